@@ -15,6 +15,13 @@ taken over the GATHERED batch as the reference's DataParallel does) + backward +
 clip_grad_norm_(10) + Adam step, i.e. everything main.py:53-66 does per batch.  Inputs are resident in HBM.
 Developer flags (not the headline line): --dense (all-ones masks), --heads 4, --no_sup_att, --h2d,
 --storage bf16 (the bf16 storage mode of BASELINE.json configs[4] at these shapes; `dtype` then says "bf16").
+
+A plain run sets up, warms up, times the --steps steps and prints the result line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the host-side split of the timed steps).  --full adds everything else the record can hold, each after the timed steps:
+the torch.profiler device-time pass, the K1 roofline lines (isolated launches and in-step events), the rocprofv3 counter passes,
+the whole-step roofline, the child runs of side_records() and the CPU baseline; the --no_* flags still drop single parts of it.
+--dump-outputs DIR writes what the last timed step computed (logits, targets, losses, temporal scores, the clipped gradient and the
+updated parameters) as DIR/<name>.npy, float32 / float64; inputs and initial weights are seeded, so two builds can be compared.
 """
 import argparse
 import json
@@ -87,7 +94,13 @@ def parse():
                     "all-ones-mask step with its in-step K1 timing, the configs[4] stress step)")
     ap.add_argument("--h2d", action="store_true", help="developer mode: every step takes its batch from pinned host memory "
                     "through tvqaplus_amd.prefetch.BatchPrefetcher (PCIe-inclusive rate for DESIGN.md; never the headline value)")
+    ap.add_argument("--full", action="store_true", help="also the measurements beside the headline line (device-time pass, rooflines, "
+                    "counter passes, child runs, CPU baseline); without it a run times the steps and prints the result line only")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_device_time = args.no_roofline = args.no_pmc = args.no_children = args.no_cpu_baseline = True
     if args.config == "stress":
         args.hsz, args.sub_words, args.storage = 256, 512, "bf16"
         args.cpu_seconds = min(args.cpu_seconds, 5.0)
@@ -98,10 +111,12 @@ EAGER_LOSS = False    # --loss fused|eager: the caller's loss line (main.py:55-6
 CLIP_FLAT = True      # --clip flat|torch: clip_grad_norm_ on the flat gradient buffer (one norm + one multiply) or torch's per-tensor form
 
 
-def train_step(model, batch, bucket, params, optimizer, n_examples, world=1):
+def train_step(model, batch, bucket, params, optimizer, n_examples, world=1, keep=None):
     from tvqaplus_amd import parallel
     bucket.zero()
-    (out, targets), att_loss, _, t_loss, _ = model(batch)
+    (out, targets), att_loss, _, t_loss, t_scores = model(batch)
+    if keep is not None:       # --dump-outputs: the step's outputs as its caller receives them
+        keep.update(logits=out, targets=targets, att_loss=att_loss, temporal_loss=t_loss, temporal_scores=t_scores)
     # main.py:59 -- len(qids) / len(targets) of the gathered batch (N_new is data dependent with add_local)
     scale = (1.0 * n_examples / len(targets)) if world == 1 else parallel.global_loss_scale(n_examples, len(targets), out.device, as_tensor=True)
     if EAGER_LOSS or out.dtype != torch.float32:
@@ -117,6 +132,27 @@ def train_step(model, batch, bucket, params, optimizer, n_examples, world=1):
         torch.nn.utils.clip_grad_norm_(params, 10.0)
     optimizer.step()
     return loss
+
+
+DUMP_LIMIT = 64 << 20     # bytes over all files of --dump-outputs
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each tensor (or number) as path/<name>.npy -- float64 stays float64, integers become float64 (exact), every
+    other float type float32.  An array that would take the total past DUMP_LIMIT is replaced by a fixed, seeded sample of its
+    elements (flat, in index order: the same positions for the same shape in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    used = 0
+    for name in sorted(arrays):
+        v = arrays[name]
+        t = (v.detach() if torch.is_tensor(v) else torch.tensor(v)).cpu()
+        a = (t.double() if (t.dtype == torch.float64 or not t.is_floating_point()) else t.float()).numpy()
+        if used + a.nbytes > DUMP_LIMIT:
+            keep = max(0, DUMP_LIMIT - used) // a.itemsize
+            a = a.reshape(-1)[torch.randperm(a.size, generator=torch.Generator().manual_seed(2018))[:keep].sort().values.numpy()]
+        np.save(os.path.join(path, name + ".npy"), a)
+        used += a.nbytes
 
 
 def _profile_traffic(name, kernel="str_attn_fwd"):
@@ -477,7 +513,7 @@ def child_bench(extra, env=None, timeout=240):
     """One more bench.py as a child process (its own HIP context: environment switches of the library are read once per process),
     N = 1, without CPU baseline / counter passes / children of its own.  Returns its JSON record or {"error": ...}."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--no_cpu_baseline", "--no_pmc", "--no_children"] + list(extra)
+    cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no_cpu_baseline", "--no_pmc", "--no_children"] + list(extra)
     e = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
@@ -802,18 +838,22 @@ def main():
         for lr in {args.regions, args.sub_words}:
             if lr <= 64:
                 k1_ev[lr] = [(lib.stage_timer_create(), lib.stage_timer_create()) for _ in range(args.steps)]
+    last = {} if args.dump_outputs else None
     sync()
     t0 = time.perf_counter()
     marks[0].record(stream)
     for i in range(args.steps):
         for lr, evs in k1_ev.items():
             lib.stage_k1_fwd_timer(evs[i][0], evs[i][1], lr)
-        loss = train_step(model, nxt(), bucket, params, optimizer, n_local, world)
+        loss = train_step(model, nxt(), bucket, params, optimizer, n_local, world, keep=last if i == args.steps - 1 else None)
         marks[i + 1].record(stream)
     t_issued = time.perf_counter()
     sync()
     dt = time.perf_counter() - t0
     lib.stage_k1_fwd_timer(None, None, 0)
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, dict(last, loss=loss, grad=bucket.flat,
+                                             params=torch.cat([p.detach().reshape(-1) for p in params])))
     k1_in_step = {}
     for lr, evs in k1_ev.items():
         ts = sorted(lib.stage_timer_elapsed_ms(a, b) for a, b in evs)

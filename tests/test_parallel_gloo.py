@@ -50,8 +50,8 @@ def _worker(rank, world, port, q):
     bucket.all_reduce()
     counts = [parallel.shard_range(5, rr, world)[1] - parallel.shard_range(5, rr, world)[0] for rr in range(world)]
     logits = parallel.all_gather_outputs(out["logits"].detach(), counts)
-    if rank == 0:
-        q.put((bucket.flat.clone(), logits))
+    if rank == 0:   # numpy copies travel by value: a shared tensor would need this process alive until the parent has read it
+        q.put((bucket.flat.detach().numpy().copy(), logits.detach().numpy().copy()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -68,7 +68,7 @@ def test_sharded_step_equals_full_batch():
     procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
     for p in procs:
         p.start()
-    flat, logits = q.get(timeout=240)
+    flat, logits = (torch.from_numpy(a) for a in q.get(timeout=240))
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -141,7 +141,7 @@ def _worker_add_local(rank, world, port, q):
     bucket.all_reduce()
     none_after = [k for (k, p) in model.named_parameters() if p.grad is None]
     if rank == 0:
-        q.put((bucket.flat.clone(), scale, n_new, none_after))
+        q.put((bucket.flat.detach().numpy().copy(), scale, n_new, none_after))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -159,6 +159,7 @@ def test_sharded_add_local_step_with_reference_loss():
     for p in procs:
         p.start()
     flat, scale, n_new0, none_after = q.get(timeout=240)
+    flat = torch.from_numpy(flat)
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
@@ -221,7 +222,7 @@ def _worker_candidates(rank, world, port, q, n_examples):
         ev = torch.zeros(0, 0)
     gathered = layout.gather_logits_world(ev)
     if rank == 0:
-        q.put((bucket.flat.clone(), gathered, (layout.E, layout.C)))
+        q.put((bucket.flat.detach().numpy().copy(), gathered.detach().numpy().copy(), (layout.E, layout.C)))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -240,6 +241,7 @@ def test_candidate_sharded_step_equals_single_process(n_examples, expect):
     for p in procs:
         p.start()
     flat, gathered, ec = q.get(timeout=400)
+    flat, gathered = torch.from_numpy(flat), torch.from_numpy(gathered)
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0

@@ -75,7 +75,8 @@ def _worker(rank, world, port, q, mode, n_examples):
         gathered = layout.gather_logits_world(ev)
     torch.cuda.synchronize()
     if rank == 0:
-        q.put((bucket.flat.cpu(), gathered.cpu(), float(scale)))
+        # numpy copies travel by value: a shared tensor would need this process alive until the parent has read it
+        q.put((bucket.flat.cpu().numpy().copy(), gathered.cpu().numpy().copy(), float(scale)))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -102,7 +103,8 @@ def _run(world, mode, n_examples, port_base):
     procs = [ctx.Process(target=_worker, args=(r, world, port, q, mode, n_examples)) for r in range(world)]
     for p in procs:
         p.start()
-    res = q.get(timeout=500)
+    flat, gathered, scale = q.get(timeout=500)
+    res = torch.from_numpy(flat), torch.from_numpy(gathered), scale
     for p in procs:
         p.join(timeout=120)
         assert p.exitcode == 0
@@ -156,7 +158,7 @@ def test_bench_two_ranks_sharing_one_gpu(hip_device):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--bsz", "2", "--frames", "12", "--regions", "8", "--sub_words", "10", "--qa_words", "9", "--hsz", "64",
-           "--no_cpu_baseline", "--no_roofline"]
+           "--full", "--no_cpu_baseline", "--no_roofline"]
     env = dict(os.environ, STAGE_BENCH_SHARED_GPU="1")
     out = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=800)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -1,9 +1,9 @@
-"""Copies the round profile set from gpurun_out/ (tools/round_profile.sh TAG) into profiles/ with the headers the readers
+"""Copies the round profile set from $OUT (default tool_out/; tools/round_profile.sh TAG) into profiles/ with the headers the readers
 (bench.py: _profile_traffic, the judge) expect.  python tools/collect_profiles.py r02"""
 import os, shutil, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TAG = sys.argv[1] if len(sys.argv) > 1 else "r05"
-G, P = os.path.join(ROOT, "gpurun_out"), os.path.join(ROOT, "profiles")
+G, P = os.path.join(ROOT, os.environ.get("OUT", "tool_out")), os.path.join(ROOT, "profiles")
 HEAD = ("# round %s: rocprofv3 PMC passes (counters only + kernel trace; tools/pmc_run.sh), averages per dispatch; FETCH_SIZE / WRITE_SIZE in KiB\n"
         "# FETCH_SIZE x2 per MI355X_MICROARCH.md (gfx950 counts the 128-byte requests of wide loads as 64 B)\n" % TAG[1:].lstrip("0"))
 

@@ -3,10 +3,11 @@
 export TMPDIR=/tmp
 R=${GRAFT_REPO_ROOT:-/root/repo}
 NAME=$1; PAT=$2; shift 2
-OUT=$R/gpurun_out/pmc_$NAME
-rm -rf $OUT; mkdir -p $OUT
 cd $R
-run() { n=$1; shift; rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $OUT/$n -o $n -- "${CMD[@]}" > $OUT/$n.log 2>&1; }
+OUT=${OUT:-tool_out}
+D=$OUT/pmc_$NAME
+rm -rf $D; mkdir -p $D
+run() { n=$1; shift; rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d $D/$n -o $n -- "${CMD[@]}" > $D/$n.log 2>&1; }
 CMD=("$@")
 run p1 SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS
 run p2 SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VMEM
@@ -14,6 +15,6 @@ run p3 SQ_INST_CYCLES_VMEM_WR SQ_INST_CYCLES_VMEM_RD SQ_WAIT_INST_LDS SQ_LDS_IDX
 run p4 GRBM_GUI_ACTIVE
 run p5 FETCH_SIZE
 run p6 WRITE_SIZE
-python tools/pmc_summarize.py $OUT "$PAT" > $R/gpurun_out/pmc_$NAME.txt
-rm -rf $OUT
-cat $R/gpurun_out/pmc_$NAME.txt
+python tools/pmc_summarize.py $D "$PAT" > $OUT/pmc_$NAME.txt
+rm -rf $D
+cat $OUT/pmc_$NAME.txt
