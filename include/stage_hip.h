@@ -27,7 +27,7 @@ extern "C" {
 #define STAGE_ERR_WORKSPACE (-2)  /* workspace too small */
 
 /* ---- library info -------------------------------------------------------------------------------------------- */
-#define STAGE_HIP_ABI_VERSION 5   /* what stage_hip_abi_version() of a matching library returns; bumped whenever a symbol or a signature changes */
+#define STAGE_HIP_ABI_VERSION 5   /* what stage_hip_abi_version() of a matching library returns; bumped when an existing symbol's signature or meaning changes (added symbols keep it) */
 int stage_hip_abi_version(void);
 const char* stage_hip_error_string(int code);
 /* Measurement helpers (bench.py; no reference counterpart): events for hosts without a HIP binding, and a one-shot hook that makes the
@@ -445,6 +445,22 @@ int stage_att_loss_fwd(const float* scores, const long long* flat, long long M, 
                        float* loss, void* stream);
 int stage_att_loss_bwd(const long long* flat, const float* coef, const float* gout, long long M, float* dS, long long n_scores,
                        void* stream);
+/* Selected rows of the attention map (csrc/score_rows.hip): K rows of Lr <= 64 scores, row k = scores[row_off[k] .. + Lr), one
+ * wavefront per row.  Ties: the lower region index first; +0 == -0.  A row with row_off[k] < 0 or row_off[k] + Lr > n_scores is
+ * never read and gets a sentinel (cnt = -1 / flat_neg = -1), as does a pair slot whose position is not below the row's negatives.
+ * stage_att_predict (model/stage.py:748-806): the regions with score >= thd (fp32 compare) in ASCENDING score order:
+ *   cnt (K) int32, val (K, Lr) the scores, idx (K, Lr) int32 the regions; slots past cnt[k] hold val = 0, idx = -1.
+ * stage_att_hard_negatives (model/stage.py:557-611): negbits (K) bit r = region r is a labelled negative of row k; pair slots
+ *   [slot_begin[k], slot_begin[k + 1]) belong to row k (slot_begin: K + 1 int32, M slots in all); slot_q (M) = position of the
+ *   slot's negative in the DESCENDING score order of the row's negatives (a NaN score sorts last).
+ *   flat_neg (M) int64 = row_off[k] + region: the negative half of stage_att_loss_fwd's `flat`.
+ * stage_score_rows_supported: 1 for 1 <= Lr <= 64 (needs no GPU); the other two return STAGE_ERR_SHAPE where it says 0.        */
+int stage_score_rows_supported(int Lr);
+int stage_att_predict(const float* scores, const long long* row_off, int K, int Lr, long long n_scores, float thd, int* cnt,
+                      float* val, int* idx, void* stream);
+int stage_att_hard_negatives(const float* scores, const long long* row_off, const unsigned long long* negbits,
+                             const int* slot_begin, const int* slot_q, int K, int M, int Lr, long long n_scores,
+                             long long* flat_neg, void* stream);
 /* G6 proposal pooling + answer classifier (model/stage.py:420-467, 526-536): first (N*NA, Li, D), mask (N*NA, Li), glob / idx_g =
  * stage_masked_max_fwd(first, mask) computed ahead; meta (device int32) = src[P] | win[2P] | inv[2N] (proposal -> example, frame
  * window [st, ed), example -> its <= 2 proposals or -1).  logits (P*NA).  params / grads: ln_g ln_b W c (2D wide); seeds[1].

@@ -134,6 +134,10 @@ SIGNATURES = {
     "stage_train_loss": (I, [P, P, P, P, P, F, F, F, P, P, I, I, P]),
     "stage_att_loss_fwd": (I, [P, P, LL, I, F, F, P, P, P]),
     "stage_att_loss_bwd": (I, [P, P, P, LL, P, LL, P]),
+    # selected rows of the attention map (csrc/score_rows.hip): box prediction, rank order of a row's negatives
+    "stage_score_rows_supported": (I, [I]),
+    "stage_att_predict": (I, [P, P, I, I, LL, F, P, P, P, P]),
+    "stage_att_hard_negatives": (I, [P, P, P, P, P, I, I, I, LL, P, P]),
     "stage_grp_pool_cls_arena_bytes": (SZ, [LL, I, I]),
     "stage_grp_pool_cls_fwd": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, LL, F, P, P]),
     "stage_grp_pool_cls_bwd_tmp_bytes": (SZ, [LL, I, I]),

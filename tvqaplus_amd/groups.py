@@ -746,3 +746,56 @@ def att_loss(scores, flat, M: int, loss_type: str, alpha: float, margin: float):
     if loss_type not in ("lse", "hinge"):
         raise NotImplementedError("Only support hinge and lse")
     return _AttLoss.apply(scores, flat, M, loss_type == "hinge", alpha, margin)
+
+
+def score_rows_supported(Lr: int) -> bool:
+    """The row kernels of csrc/score_rows.hip hold one region per lane of a wavefront: 1 <= Lr <= 64."""
+    return bool(_lib.load().stage_score_rows_supported(int(Lr)))
+
+
+def att_predict(scores, row_off, thd: float, out: Optional[torch.Tensor] = None):
+    """Box prediction on K selected rows of a contiguous fp32 score tensor (model/stage.py:748-806): row k =
+    ``scores.reshape(-1)[row_off[k] : row_off[k] + Lr]``, Lr = the tensor's last dimension.  Returns ``cnt (K) int32, val (K, Lr)
+    float32, idx (K, Lr) int32``: the regions with score >= thd in ascending score order (ties: lower region first), the rest
+    filled with 0 / -1; ``cnt = -1`` for a row outside the tensor (never read).  The three are views of ONE int32 buffer of
+    K * (2 Lr + 1) words (``out``, allocated here when absent), so a caller brings them to the host in a single copy."""
+    Lr = int(scores.shape[-1])
+    if not score_rows_supported(Lr):
+        raise Unsupported("stage_att_predict: Lr = %d" % Lr)
+    s = _chk(scores.detach(), "scores")
+    row_off = _chk(row_off, "row offsets", torch.int64)
+    K = row_off.numel()
+    words = K * (2 * Lr + 1)
+    if out is None:
+        out = torch.empty(words, dtype=torch.int32, device=s.device)
+    elif not (out.is_cuda and out.dtype == torch.int32 and out.is_contiguous() and out.numel() == words and out.device == s.device):
+        raise ValueError("att_predict: `out` must be a contiguous int32 device tensor of K * (2 Lr + 1) elements")
+    cnt, val, idx = out[:K], out[K:K + K * Lr].view(torch.float32).view(K, Lr), out[K + K * Lr:].view(K, Lr)
+    with torch.cuda.device(s.device):
+        _rc(_lib.load().stage_att_predict(s.data_ptr(), row_off.data_ptr(), K, Lr, s.numel(), float(thd), cnt.data_ptr(),
+                                          val.data_ptr(), idx.data_ptr(), _stream()), "stage_att_predict")
+    return cnt, val, idx
+
+
+def att_hard_negatives(scores, row_off, negbits, slot_begin, slot_q, out):
+    """Hard-negative sampling on the device (model/stage.py:557-611): for every pair slot m of row k (``slot_begin[k] <= m <
+    slot_begin[k + 1]``) ``out[m] = row_off[k] + region``, the region at position ``slot_q[m]`` of the row's labelled negatives
+    (``negbits[k]``, bit r = region r; int64 holding the uint64 pattern) in descending score order, ties: lower region first.
+    ``out``: (M) int64 -- the negative half of the index tensor ``att_loss`` takes.  -1 for a row outside the tensor or a position
+    not below the row's negative count."""
+    Lr = int(scores.shape[-1])
+    if not score_rows_supported(Lr):
+        raise Unsupported("stage_att_hard_negatives: Lr = %d" % Lr)
+    s = _chk(scores.detach(), "scores")
+    row_off, negbits = _chk(row_off, "row offsets", torch.int64), _chk(negbits, "negative bits", torch.int64)
+    slot_begin, slot_q = _chk(slot_begin, "slot_begin", torch.int32), _chk(slot_q, "slot_q", torch.int32)
+    K, M = row_off.numel(), slot_q.numel()
+    if negbits.numel() != K or slot_begin.numel() != K + 1:
+        raise ValueError("att_hard_negatives: negbits (K) / slot_begin (K + 1) do not match row_off (K)")
+    if not (out.is_cuda and out.dtype == torch.int64 and out.is_contiguous() and out.numel() == M and out.device == s.device):
+        raise ValueError("att_hard_negatives: `out` must be a contiguous int64 device tensor of M elements")
+    with torch.cuda.device(s.device):
+        _rc(_lib.load().stage_att_hard_negatives(s.data_ptr(), row_off.data_ptr(), negbits.data_ptr(), slot_begin.data_ptr(),
+                                                 slot_q.data_ptr(), K, M, Lr, s.numel(), out.data_ptr(), _stream()),
+            "stage_att_hard_negatives")
+    return out

@@ -311,6 +311,7 @@ class STAGE(nn.Module):
             raise ValueError("opt.storage_dtype must be 'fp32' or 'bf16', got %r" % sd)
         self.storage = torch.bfloat16 if sd in ("bf16", "bfloat16") else torch.float32
         self._span_host = None      # pinned landing buffer of the per-step proposal spans (get_proposals)
+        self._qas_host = None       # pinned landing buffer of the word ids in inference mode (box prediction's row table)
         self._meta_stage = None     # pinned staging of the per-step proposal bookkeeping (_proposals_grouped)
         # counter-based dropout stream (csrc/common.h): seeded lazily from the seed of torch's default generator at the first
         # use (so torch.manual_seed() before training takes effect, as for the reference's nn.Dropout) and mixed with the
@@ -933,6 +934,16 @@ class STAGE(nn.Module):
         sub_mask_f = batch.sub_mask.float() if self.sub_flag else None
         vid_mask_f = batch.vid_mask.float() if self.vfeat_flag else None
         dev = batch.qas_bert.device
+        qas_arrived = None
+        if self.inference_mode and self.vfeat_flag and torch.is_tensor(batch.qas) and batch.qas.is_cuda:
+            # box prediction (att_host.get_att_prediction) selects its rows by the word ids: their host copy (25 KB) is requested HERE,
+            # non-blocking into pinned memory, so that the row table needs no read-back of its own once the forward is queued
+            if self._qas_host is None or self._qas_host.shape != batch.qas.shape or self._qas_host.dtype != batch.qas.dtype:
+                self._qas_host = torch.empty(batch.qas.shape, dtype=batch.qas.dtype, pin_memory=True)
+            with torch.cuda.device(batch.qas.device):
+                self._qas_host.copy_(batch.qas, non_blocking=True)
+                qas_arrived = torch.cuda.Event()
+                qas_arrived.record(torch.cuda.current_stream(batch.qas.device))
         streams = int(self.use_streams) if dev.type == "cuda" else 0
         if streams > 3 and os.environ.get("STAGE_STREAMS_UNSAFE4") is None and not (self._grouped() and self.storage == torch.float32 and self.input_encoder.stacked_encoderBlocks[0].num_heads == 0):
             # level 4 (two attention forwards side by side) only on the fp32 K-group path, where steps reproduce level 0 bit for bit; on the
@@ -1049,17 +1060,30 @@ class STAGE(nn.Module):
         # the host is about to wait for the device at the proposal read-back anyway: ~10 ms of slack, the 3-11 ms of index
         # building hide completely.  Built at the top of the step they left the device idle for ~2 ms (the previous
         # step's queue drained first); the reference builds them after the forward, on the critical path.
+        # Hard-negative mode: the same slot takes the score-free half (att_host.build_hard_plan: rows, negatives, rank positions,
+        # the reference's draws); get_att_loss resolves the positions into regions on the device once the scores exist.
         att_pairs = None
         if (self.use_sup_att and self.training and self.vfeat_flag and not self.inference_mode
-                and not bool(_opt(batch, "use_hard_negatives", False)) and _opt(batch, "att_pairs", None) is None):
-            from .att_host import AttPairs, build_att_pairs, targets_on_device_ok
-            on_dev = targets_on_device_ok(self, batch, NA)       # no host copy of the answers: their offset is added on the device
-            pos, neg = build_att_pairs(self, batch, None, n_local_candidates=NA, placeholder_targets=on_dev)
-            if pos is not None:
-                Li_v, Lr_v = batch.vid.shape[1:3]
-                att_pairs = AttPairs(pos, neg, (N, NA, Li_v, batch.qas_mask.shape[-1], Lr_v), batch.vid.device,
-                                     getattr(self, "_att_stage", None), target_dev=batch.target if on_dev else None)
-                self._att_stage = att_pairs.stage
+                and _opt(batch, "att_pairs", None) is None):
+            from . import att_host
+            Li_v, Lr_v = batch.vid.shape[1:3]
+            att_shape = (N, NA, Li_v, batch.qas_mask.shape[-1], Lr_v)
+            if not bool(_opt(batch, "use_hard_negatives", False)):
+                on_dev = att_host.targets_on_device_ok(self, batch, NA)       # no host copy of the answers: their offset is added on the device
+                pos, neg = att_host.build_att_pairs(self, batch, None, n_local_candidates=NA, placeholder_targets=on_dev)
+                if pos is not None:
+                    att_pairs = att_host.AttPairs(pos, neg, att_shape, batch.vid.device, getattr(self, "_att_stage", None),
+                                                  target_dev=batch.target if on_dev else None)
+                    self._att_stage = att_pairs.stage
+            elif (batch.vid.is_cuda and self.storage == torch.float32 and groups.score_rows_supported(Lr_v)
+                  and (_opt(batch, "target_list", None) is not None or att_host.device_only_targets(self, batch, NA))):
+                # (device-only targets of a candidate-sharded batch: the host path and its read-back, as in random mode)
+                on_dev = _opt(batch, "target_list", None) is None
+                plan = att_host.build_hard_plan(self, batch, n_local_candidates=NA, placeholder_targets=on_dev)
+                if plan is not None:
+                    att_pairs = att_host.AttHardPairs(plan, att_shape, batch.vid.device, getattr(self, "_att_stage", None),
+                                                      target_dev=batch.target if on_dev else None)
+                    self._att_stage = att_pairs.stage
         ctx_m = vid_mask if self.vfeat_flag else sub_mask       # the statement mask's context side (model/stage.py:386)
         factors = ((qas_mask != 0).any(-1), ctx_m.sum(-1) != 0)
         out, target, t_scores = self.classfier_head_multi_proposal(
@@ -1070,11 +1094,15 @@ class STAGE(nn.Module):
 
         if self.inference_mode:
             from .att_host import get_att_prediction
+            words = batch.qas
+            if qas_arrived is not None:
+                qas_arrived.synchronize()
+                words = self._qas_host
             return {
                 "answer": out,
                 "t_scores": F.softmax(t_scores, dim=2),
                 "att_predictions": get_att_prediction(
-                    scores=other_outputs["vid_raw_s"], object_vocab=batch.eval_object_word_ids, words=batch.qas,
+                    scores=other_outputs["vid_raw_s"], object_vocab=batch.eval_object_word_ids, words=words,
                     vid_names=batch.vid_name, qids=batch.qid, img_indices=batch.image_indices, boxes=batch.boxes,
                     start_indices=batch.anno_st_idx) if self.vfeat_flag else None,
             }
