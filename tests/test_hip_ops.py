@@ -568,7 +568,7 @@ def test_k1_d128_region_sweep(ops, Lr):
                                               (2, 7, 20, 40, "pad"), (1, 5, 50, 40, "valid"), (1, 5, 50, 40, "pad")])
 def test_k1_backward_fused_paths(ops, N, Li, Lr, Lqa, ext):
     """Single-pass backward (csrc/str_attn_bwd_fused.hip), every dispatch: uniform row walk with dA kept in LDS (Lr = 20,
-    8), uniform walk with the re-read from L2 (Lr = 50, 36, or STAGE_K1_BWD_NOLDSA), per-lane walk (Lqa = 23, 12); with
+    8), uniform walk with the re-read from L2 (Lr = 50, 36), per-lane walk (Lqa = 23, 12); with
     the gradient on raw_s and without it (padded region tiles / empty frames skipped, their gradients are exact zeros).
     ext: True = dense gradient on raw_s (every column processed); "valid" = sparse, on valid regions only, as the
     supervised-attention loss produces it (the skips stay on); "pad" = a few non-zeros on padded regions and in an empty
@@ -622,8 +622,8 @@ def test_k1_backward_fused_paths(ops, N, Li, Lr, Lqa, ext):
         ops._K1_BWD_UNFUSED = old_flag
     check("dC fused vs three-kernel", fused[0], three[0], 2e-4)
     check("dQ fused vs three-kernel", fused[1], three[1], 2e-4)
-    # the developer switches select kernels inside the library at first use (static) -- only the python-side switch above
-    # can be toggled per call; STAGE_K1_BWD_NOLDSA is exercised by tools/k1_bwd_times.py
+    # which fused kernel runs is decided by the shape alone (the parametrisation covers every dispatch); the python-side
+    # flag above selects the three-kernel path per call
     again = run()
     assert torch.equal(fused[0], again[0]) and torch.equal(fused[1], again[1])   # run-to-run deterministic
 

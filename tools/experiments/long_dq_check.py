@@ -1,5 +1,5 @@
-"""stage_str_attn_long_bwd_qm on random bf16 operands: dQraw / dQn of the 32-region bf16 kernel against fp64 products (and, with
-STAGE_LONG_DQ16=1, of the 16-region fp32-MFMA kernel).  python tools/experiments/long_dq_check.py [N Li Lr Lqa]"""
+"""stage_str_attn_long_bwd_qm on random bf16 operands: dQraw / dQn of the 32-region bf16 kernel against fp64 products.
+python tools/experiments/long_dq_check.py [N Li Lr Lqa]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from tvqaplus_amd import _lib

@@ -825,7 +825,6 @@ inline int cw_grid() {                                    // one persistent work
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0)
             cus = n > 512 ? 512 : n;
         else cus = 256;
-        if (getenv("STAGE_CW_GRID")) cus = atoi(getenv("STAGE_CW_GRID"));
     }
     return cus;
 }

@@ -514,7 +514,7 @@ __global__ __launch_bounds__(256) void cf_reduce_seg_kernel(const float* __restr
 void cf_chunks(long long groups, int rep, int mode, int* CH, int* fpc) {
     // ~4 workgroups per resident slot (2 per CU): with about one workgroup per slot the last few run alone.  MODE 2 walks the
     // frames four at a time: chunks of a multiple of four frames
-    static const long wg_target = getenv("STAGE_CF_WGS") ? atol(getenv("STAGE_CF_WGS")) : 2048;       // (developer sweep: 1536-2560 measured 1-2 % faster than 4096, 1024 10 % slower)
+    constexpr long wg_target = 2048;       // (sweep: 1536-2560 measured 1-2 % faster than 4096, 1024 10 % slower)
     int ch = (int)((wg_target + groups - 1) / groups);
     if (ch > rep) ch = rep;
     if (ch < 1) ch = 1;
@@ -524,10 +524,7 @@ void cf_chunks(long long groups, int rep, int mode, int* CH, int* fpc) {
     *CH = (rep + f - 1) / f;
 }
 inline size_t cf_align(size_t v) { return (v + 255) & ~(size_t)255; }
-inline long cf_flat_grid() {                          // MODE 0: workgroups that stride the 32-row tiles (developer sweep: STAGE_CF_FLAT_GRID)
-    static const long g = getenv("STAGE_CF_FLAT_GRID") ? atol(getenv("STAGE_CF_FLAT_GRID")) : 1024;
-    return g;
-}
+constexpr long CF_FLAT_GRID = 1024;                   // MODE 0: workgroups that stride the 32-row tiles
 inline int cf_mode(int rep, int inner) { return rep == 1 ? 0 : (inner <= 32 ? 1 : (inner == 40 ? 2 : -1)); }
 }  // namespace
 
@@ -545,7 +542,7 @@ extern "C" size_t stage_cat3_dx_ln_bwd_ws_bytes(long long rows, int D, int rep, 
         cf_chunks(rows / ((long long)rep * inner), rep, cf_mode(rep, inner), &CH, &fpc);
         wg = (size_t)(rows / ((long long)rep * inner)) * CH;
     } else {
-        wg = (size_t)cf_flat_grid();
+        wg = (size_t)CF_FLAT_GRID;
     }
     size_t b = cf_align((size_t)CF_WFRAG * sizeof(uint4)) + 256;                 // weight image + scale word
     b += cf_align(wg * 2 * 3 * CF_D * sizeof(float));                            // d gamma / d beta partials
@@ -585,7 +582,7 @@ extern "C" int stage_cat3_dx_ln_bwd(const float* dy, const unsigned* relu_mask, 
         da_out = (float*)wsp;                                  // slabs [G][CH][inner][D]
     } else {
         const long tiles = (long)((rows + 31) / 32);
-        grid = (int)(tiles < cf_flat_grid() ? tiles : cf_flat_grid());
+        grid = (int)(tiles < CF_FLAT_GRID ? tiles : CF_FLAT_GRID);
     }
 #define CF_LAUNCH(DR, MD)                                                                                                          \
     hipLaunchKernelGGL((cf_bwd_kernel<DR, MD>), dim3(grid), dim3(256), lds, st, dy, relu_mask, img, w_up, a, b, mean, rstd, gamma,    \
@@ -634,8 +631,6 @@ extern "C" int stage_cat3_dx_ln_bwd_rag(const float* dy, const unsigned* relu_ma
                                         size_t ws_bytes, void* stream) {
     if (!stage_cat3_dx_ln_bwd_rag_supported(rows, fc_rows, D, groups, max_frames, Lqa)) return STAGE_ERR_SHAPE;
     if (ws_bytes < stage_cat3_dx_ln_bwd_rag_ws_bytes(groups, max_frames, Lqa)) return STAGE_ERR_WORKSPACE;
-    static const bool no_balance = getenv("STAGE_CF_NO_BALANCE") != nullptr;     // developer switch: the (group, chunk) grid
-    if (no_balance) wtab = nullptr;
     hipStream_t st = (hipStream_t)stream;
     char* wsp = (char*)ws;
     uint4* img = (uint4*)wsp;
@@ -686,6 +681,7 @@ extern "C" int stage_cat3_dx_ln_bwd_rag(const float* dy, const unsigned* relu_ma
 namespace {
 constexpr int CFF_KS = 3 * CF_D / 16;             // 24 k-steps of the 32x32x16 MFMA
 constexpr int CFF_WFRAG = 2 * 4 * CFF_KS * 64;    // uint4 fragments of the forward weight image
+constexpr long CFF_GRID_CAP = 3072;               // workgroups that stride the 32-row tiles (grid-size sweep)
 
 // Wimg[plane][wave w][k-step ks][lane] = the 8 fp16 of B-operand lane (col n = 32 w + (lane & 31), k = 16 ks + 8 (lane >> 5) + e) of
 // W[n][k]  (W = the Linear's (D, 3D) weight)
@@ -941,8 +937,7 @@ extern "C" int stage_cat3_ln_gemm_fwd(const float* a, const float* b, const floa
     const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
     const size_t lds = (size_t)CFF_KS * 2 * 64 * 16 + 32 * 4;
     const long tiles = (long)((rows + 31) / 32);
-    static const long grid_cap = getenv("STAGE_CFF_GRID") ? atol(getenv("STAGE_CFF_GRID")) : 3072;   // (developer sweep)
-    const int grid = (int)(tiles < grid_cap ? tiles : grid_cap);
+    const int grid = (int)(tiles < CFF_GRID_CAP ? tiles : CFF_GRID_CAP);
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)cff_fwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);
@@ -975,8 +970,7 @@ extern "C" int stage_cat3_ln_gemm_fwd_rag(const float* a, const float* b, const 
     const float inv_keep = p_drop > 0.f ? 1.0f / (1.0f - p_drop) : 1.0f;
     const size_t lds = (size_t)CFF_KS * 2 * 64 * 16 + 32 * 4;
     const long tiles = (long)((rows + 31) / 32);
-    static const long grid_cap = getenv("STAGE_CFF_GRID") ? atol(getenv("STAGE_CFF_GRID")) : 3072;
-    const int grid = (int)(tiles < grid_cap ? tiles : grid_cap);
+    const int grid = (int)(tiles < CFF_GRID_CAP ? tiles : CFF_GRID_CAP);
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)cff_fwd_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024);

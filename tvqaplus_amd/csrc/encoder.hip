@@ -3,7 +3,6 @@
 //   * depthwise Conv1d(k, groups=D, zero padding k//2) along L of (M, L, D) tensors, forward and backward
 // The 1x1 pointwise conv + ReLU + residual is stage_gemm_nt's epilogue; the LayerNorms are rowops.hip.
 // Padded sequence positions are NOT masked anywhere here (bug-compatible with the reference).
-#include <stdlib.h>
 #include "common.h"
 #include "../../include/stage_hip.h"
 
@@ -61,67 +60,11 @@ __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const T* __restrict__ i
     }
 }
 
-// din[m,l,:] = sum_t w[:,t] * dout[m, l-t+pad, :] ; partial dw[t][d], db[d] per block.
-template <typename T>
-__global__ __launch_bounds__(256) void dwconv_bwd_kernel(const T* __restrict__ dout, const T* __restrict__ in,
-                                                         const float* __restrict__ w, T* __restrict__ din,
-                                                         float* __restrict__ part, long rows, int L, int D, int k) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];  // wT [k][D]  then reduction scratch
-    for (int i = threadIdx.x; i < k * D; i += blockDim.x) {
-        const int t = i / D, d = i % D;
-        sm[i] = w[d * k + t];
-    }
-    __syncthreads();
-    const int D4 = D >> 2, pad = k >> 1;
-    const int rpi = blockDim.x / D4;  // rows per iteration of this block
-    const int q = threadIdx.x % D4, rsub = threadIdx.x / D4;
-    const bool active = rsub < rpi;
-    float4 aw[KMAX], ab = f4zero();
-#pragma unroll
-    for (int t = 0; t < KMAX; t++) aw[t] = f4zero();
-    if (active) {
-        for (long row = (long)blockIdx.x * rpi + rsub; row < rows; row += (long)gridDim.x * rpi) {
-            const int l = (int)(row % L);
-            const float4 go = ldv4(dout + (row * D4 + q) * 4);
-            ab = f4add(ab, go);
-            float4 gi = f4zero();
-#pragma unroll
-            for (int t = 0; t < KMAX; t++) {
-                if (t < k) {
-                    const int lf = l + t - pad;  // forward tap: out[l] uses in[l+t-pad]
-                    if (lf >= 0 && lf < L)
-                        aw[t] = f4add(aw[t], f4mul(go, ldv4(in + ((row + (t - pad)) * D4 + q) * 4)));
-                    const int lb = l - t + pad;  // din[l] collects dout[l-t+pad] * w[t]
-                    if (lb >= 0 && lb < L)
-                        gi = f4add(gi, f4mul(ldv4(dout + ((row - t + pad) * D4 + q) * 4), ld4(&sm[t * D + 4 * q])));
-                }
-            }
-            stv4(din + (row * D4 + q) * 4, gi);
-        }
-    }
-    __syncthreads();
-    // block reduce: scratch [rpi][(k+1)][D]
-    float* red = sm;
-    if (active) {
-#pragma unroll
-        for (int t = 0; t < KMAX; t++)
-            if (t < k) st4(&red[((size_t)rsub * (k + 1) + t) * D + 4 * q], aw[t]);
-        st4(&red[((size_t)rsub * (k + 1) + k) * D + 4 * q], ab);
-    }
-    __syncthreads();
-    const int C = (k + 1) * D;
-    for (int c = threadIdx.x; c < C; c += blockDim.x) {
-        float s = 0.f;
-        for (int r = 0; r < rpi; r++) s += red[(size_t)r * C + c];
-        part[(size_t)blockIdx.x * C + c] = s;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// Sliding-window versions (the ones that run): a thread owns one float4 column of one chunk of <= 48 positions of one
+// Sliding-window versions (every D <= 1024; the forward kernel above takes wider rows): a thread owns one float4 column of one chunk of <= 48 positions of one
 // sequence and walks it, keeping the k taps of `in` (and of `dout` in the backward) in registers: every element is
 // loaded once per chunk (+ a halo of k-1 rows) by straight-line loads from clamped addresses, instead of 2k+1 guarded
-// loads per output element.  Same arithmetic order over the taps as the kernels above.
+// loads per output element.  Same arithmetic order over the taps as the kernel above.
 // ------------------------------------------------------------------------------------------------
 
 template <int KT, typename T = float>
@@ -252,7 +195,7 @@ template <typename T>
 static int dwconv_fwd_t(const T* in, const float* w, const float* bias, T* out, long long M, int L, int D, int k, void* stream) {
     if (M <= 0) return 0;
     if (D % 4 != 0 || k < 1 || k > KMAX || (k & 1) == 0) return STAGE_ERR_SHAPE;
-    if (D / 4 <= 256 && !getenv("STAGE_DWCONV_GENERIC")) {
+    if (D / 4 <= 256) {
         const int rpi = 256 / (D / 4);
         const int clen = stage_chunk_len(L);
         const long items = (long)M * ((L + clen - 1) / clen);
@@ -294,26 +237,16 @@ static int dwconv_bwd_t(const T* dout, const T* in, const float* w, T* din, floa
         return 0;
     }
     const int rpi = 256 / (D / 4);
-    int grid;
-    size_t lds = (size_t)k * D;
-    const size_t red = (size_t)rpi * (k + 1) * D;
-    if (red > lds) lds = red;
-    if (!getenv("STAGE_DWCONV_GENERIC")) {
-        const int clen = stage_chunk_len(L);
-        const long items = (long)M * ((L + clen - 1) / clen);
-        grid = stage_grid_for(items, rpi, DW_PART_CAP);
-        const size_t ldb = red * sizeof(float);
-        switch (k) {
-            case 1: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<1, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
-            case 3: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<3, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
-            case 5: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<5, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
-            case 7: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<7, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
-            default: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<9, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
-        }
-    } else {
-        grid = stage_grid_for(M * L, rpi * 8, DW_PART_CAP);
-        hipLaunchKernelGGL(dwconv_bwd_kernel<T>, dim3(grid), dim3(256), lds * sizeof(float), st, dout, in, w, din,
-                           (float*)ws, (long)(M * L), L, D, k);
+    const size_t ldb = (size_t)rpi * (k + 1) * D * sizeof(float);
+    const int clen = stage_chunk_len(L);
+    const long items = (long)M * ((L + clen - 1) / clen);
+    const int grid = stage_grid_for(items, rpi, DW_PART_CAP);
+    switch (k) {
+        case 1: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<1, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
+        case 3: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<3, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
+        case 5: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<5, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
+        case 7: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<7, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
+        default: hipLaunchKernelGGL((dwconv_bwd_sw_kernel<9, T>), dim3(grid), dim3(256), ldb, st, dout, in, w, din, (float*)ws, (long)M, L, D, clen); break;
     }
     STAGE_LAUNCH_CHECK();
     stage_colreduce((const float*)ws, dw, db, grid, (long)(k + 1) * D, (k + 1) * D, D, k, st);

@@ -150,12 +150,9 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const float* __restrict
 
 // Shapes the streaming kernels (gemm_stream.hip: two-way fp16 split) do not take: forward-form GEMMs (NT) default to the
 // tiled split-bf16 kernel with the exact 3-way split (gemm_bf16x3.hip: fp32-level accuracy, ~15-25 % faster than the f32 MFMA
-// at these shapes); the weight-gradient form (TN) stays on the f32 MFMA, where the transposing split staging costs more than it saves.  STAGE_GEMM_F32=1 forces f32 everywhere,
-// STAGE_GEMM_SPLIT_TN=1 also routes TN through the split kernel.
+// at these shapes); the weight-gradient form (TN) stays on the f32 MFMA, where the transposing split staging costs more than it saves.  STAGE_GEMM_F32=1 forces f32 everywhere.
 extern "C" int stage_gemm_nt_bf16x3(const float* X, const float* gate, const float* W, const float* bias,
                                     const float* residual, float* Y, long long M, int N, int K, int relu, void* stream);
-extern "C" int stage_gemm_tn_bf16x3(const float* dY, const float* gate, const float* X, float* dW, float* db, long long M,
-                                    int N, int K, void* ws, size_t ws_bytes, void* stream);
 // gemm_stream.hip (gate_kind: 0 none, 1 fp32 tensor, 2 bit mask; return 1 = shape not handled there)
 int stage_gemm_nt_stream(const float* X, const void* gate, int gate_kind, const float* W, const float* bias,
                          const float* residual, float* Y, unsigned* mask_out, long long M, int N, int K, int relu,
@@ -173,11 +170,8 @@ extern "C" int stage_gemm_nt(const float* X, const float* gate, const float* W, 
     if (M <= 0 || N <= 0) return 0;
     if (K <= 0) return STAGE_ERR_SHAPE;
     if (!gemm_exact_f32()) {
-        static const bool tiled_only = getenv("STAGE_GEMM_TILED") != nullptr;   // developer switch
-        if (!tiled_only) {
-            const int rc = stage_gemm_nt_stream(X, gate, gate ? 1 : 0, W, bias, residual, Y, nullptr, M, N, K, relu, stream);
-            if (rc <= 0) return rc;                      // 1 = shape not handled by the streaming kernel
-        }
+        const int rc = stage_gemm_nt_stream(X, gate, gate ? 1 : 0, W, bias, residual, Y, nullptr, M, N, K, relu, stream);
+        if (rc <= 0) return rc;                      // 1 = shape not handled by the streaming kernel
         return stage_gemm_nt_bf16x3(X, gate, W, bias, residual, Y, M, N, K, relu, stream);
     }
     if (K <= 0) return STAGE_ERR_SHAPE;
@@ -312,7 +306,6 @@ extern "C" size_t stage_gemm_tn_ws_bytes(long long M, int N, int K) {
 
 extern "C" int stage_gemm_tn(const float* dY, const float* gate, const float* X, float* dW, float* db, long long M,
                              int N, int K, void* ws, size_t ws_bytes, void* stream) {
-    if (!gemm_exact_f32() && getenv("STAGE_GEMM_SPLIT_TN")) return stage_gemm_tn_bf16x3(dY, gate, X, dW, db, M, N, K, ws, ws_bytes, stream);
     hipStream_t st = (hipStream_t)stream;
     if (N <= 0 || K <= 0) return 0;
     if (M <= 0) {
@@ -329,9 +322,8 @@ extern "C" int stage_gemm_tn(const float* dY, const float* gate, const float* X,
     const int vecY = (N % 4 == 0) && (((uintptr_t)dY & 15) == 0) && (!gate || ((uintptr_t)gate & 15) == 0);
     const int vecX = (K % 4 == 0) && (((uintptr_t)X & 15) == 0);
     dim3 grid((N + BM - 1) / BM, (K + BN - 1) / BN, S);
-    static const bool tn_tiled = getenv("STAGE_GEMM_TN_TILED") != nullptr;   // developer switch
     int handled = 1;
-    if (!gemm_exact_f32() && !tn_tiled)
+    if (!gemm_exact_f32())
         handled = stage_gemm_tn_stream(dY, gate, gate ? 1 : 0, X, part, db ? part_b : (float*)nullptr, M, N, K, &S, &rps, stream);
     if (handled < 0 || handled > 1) return handled;
     if (handled == 0) {
@@ -356,7 +348,7 @@ extern "C" int stage_gemm_tn(const float* dY, const float* gate, const float* X,
 // the gate bytes, and the 15 MB mask of a (960000, 128) layer stays cache resident.
 // ------------------------------------------------------------------------------------------------
 extern "C" int stage_gemm_mask_supported(long long M, int N, int K) {
-    if (gemm_exact_f32() || getenv("STAGE_GEMM_TILED") || getenv("STAGE_GEMM_TN_TILED") || getenv("STAGE_GEMM_NO_MASK")) return 0;
+    if (gemm_exact_f32()) return 0;
     // forward (M,K)->(M,N), dX (M,N)->(M,K), dW: all three must be taken by the streaming kernels
     const bool fwd = K % 4 == 0 && K >= 64 && M >= 4096 && M * (long long)K * 4 < (1ll << 31);
     const bool dx = N % 4 == 0 && N >= 64 && M * (long long)N * 4 < (1ll << 31);
@@ -371,7 +363,7 @@ int stage_gemm_nt_stream_lnparam(const float* dY, const unsigned* gate_mask, con
                                  const float* rstd, const unsigned* keep_mask, float p_drop, float* dgamma, float* dbeta,
                                  long long M, int N, int K, void* ws, size_t ws_bytes, void* stream);
 extern "C" int stage_gemm_nt_lnparam_supported(long long M, int N, int K) {
-    if (gemm_exact_f32() || getenv("STAGE_GEMM_TILED") || getenv("STAGE_GEMM_NO_LNPARAM")) return 0;
+    if (gemm_exact_f32()) return 0;
     return (K % 4 == 0 && K >= 64 && N % 4 == 0 && M >= 4096 && M * (long long)K * 4 < (1ll << 31) &&
             M * (long long)N * 4 < (1ll << 31)) ? 1 : 0;
 }

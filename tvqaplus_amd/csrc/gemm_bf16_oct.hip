@@ -20,7 +20,6 @@
 //   * the workgroups that share a slab (K > 256: one per 256-column block of X, each re-reading dY) are placed on the same XCD and
 //     run at the same time: the re-read is served by that XCD's L2.
 // Algorithmic bytes: M * (N + K) * 2; MFMA work at the HBM roofline is about a quarter of the bf16 matrix-core peak.
-#include <stdlib.h>
 #include <stdint.h>
 #include "common.h"
 #include "../../include/stage_hip.h"
@@ -224,8 +223,7 @@ __global__ __launch_bounds__(256) void oct_reduce_b_kernel(const float* __restri
 
 // slabs of the octet kernel for a shape (0: not handled here)
 static int go_plan(long long M, int N, int K, int* KB, int* NB, int* Kp, long* rps) {
-    static const bool off = getenv("STAGE_GEMM_BF16_NO_OCT") != nullptr;
-    if (off || M < 8192 || N % 4 != 0 || K % 4 != 0 || N <= 128 || K < 64) return 0;
+    if (M < 8192 || N % 4 != 0 || K % 4 != 0 || N <= 128 || K < 64) return 0;
     *KB = (K + 255) / 256;
     *NB = (N + 255) / 256;
     *Kp = *KB * 256;

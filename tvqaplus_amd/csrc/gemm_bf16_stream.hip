@@ -13,7 +13,6 @@
 // (a direct store would write 8-byte pieces of 32 different lines per instruction -- what the memory system handles worst).
 // Shapes outside (K % 4 == 0, K <= 384, N % 128 == 0, M >= 4096, 8-byte aligned operands) take the 64-column variant below or the tiled kernel of
 // gemm_bf16x3.hip.
-#include <stdlib.h>
 #include "common.h"
 #include "../../include/stage_hip.h"
 
@@ -295,10 +294,6 @@ static int gb_launch64(const void* X, const void* gate, const float* W, const fl
     Kp += ((Kp / 8) % 2 == 0) ? 8 : 16;
     const size_t lds = (size_t)64 * Kp * 2 + (size_t)GB_WAVES * 32 * GB_STG * 2 + 64 * sizeof(float);
     if (lds > 160 * 1024) return 1;
-    // a gated operand in half-aligned rows with many column tiles: measured slower than the tiled kernel (2.46 M rows,
-    // 300 -> 768: 12.7 vs 9.1 ms; 240 k rows: 1.04 vs 0.88 ms)
-    static const bool tiled_gated = getenv("STAGE_GEMM_BF16_TILED_GATED") != nullptr;    // (developer switch: the rule of round 3)
-    if (tiled_gated && gate && K % 8 != 0 && N > 256) return 1;
     const long MT = (M + 31) / 32;
     const int n_tiles = (N + 63) / 64;
     long gx = (256 / n_tiles) / 8 * 8;
@@ -321,8 +316,6 @@ static int gb_launch64(const void* X, const void* gate, const float* W, const fl
 
 int stage_gemm_nt_bf16_stream(const void* X, const void* gate, const float* W, const float* bias, void* Y, long long M, int N,
                               int K, int relu, void* stream) {
-    static const bool off = getenv("STAGE_GEMM_BF16_TILED") != nullptr;   // developer switch: tiled kernel everywhere
-    if (off) return 1;
     if (M < 4096 || K % 4 != 0 || K < 64 || K > 384 || N % GB_BN != 0 ||
         ((uintptr_t)X & 7) || ((uintptr_t)Y & 15) || ((uintptr_t)W & 15) || (gate && ((uintptr_t)gate & 7)))
         return gb_launch64(X, gate, W, bias, Y, M, N, K, relu, stream);   // wide K / ragged N / 8-byte rows
@@ -513,21 +506,17 @@ __global__ __launch_bounds__(768) void gemm_tn_bf16_stream_kernel(const stage_bf
 }
 
 // slabs x interleaves of the streaming TN kernel for a shape (0: not handled)
-static int tb_plan(long long M, int N, int K, int* P, int* RS, int* KPn, int* GY, long* rps) {
+static int tb_plan(long long M, int N, int K, int* P, int* RS, int* KPn, long* rps) {
     if (M < 4096 || N % 2 != 0 || K % 2 != 0 || N < 2 || K < 2) return 0;
     *KPn = (K + 63) / 64;
-    const int total = ((N + 63) / 64) * *KPn;
+    *P = ((N + 63) / 64) * *KPn;
     // more than 12 patches need several workgroup groups, each re-reading one operand: measured slower than the tiled kernel
     // in both group orders (2.46 M rows, 768 x 300 and 768 x 256: stress step 111.4 vs 108.9 ms) -- those shapes stay tiled
-    // unless STAGE_GEMM_BF16_TN_GROUPS is set (developer switch)
-    if (total > 12 && !getenv("STAGE_GEMM_BF16_TN_GROUPS")) return 0;
-    *GY = (total + 11) / 12;                    // <= 12 waves per workgroup (768 threads: 168 registers per lane)
-    *P = (total + *GY - 1) / *GY;
-    *RS = *GY == 1 ? (12 / *P) : 1;
+    if (*P > 12) return 0;                      // <= 12 waves per workgroup (768 threads: 168 registers per lane)
+    *RS = 12 / *P;
     if (*RS > 1 + 8 / *P) *RS = 1 + 8 / *P;    // LDS for the in-workgroup sum: (RS - 1) * P * 16.5 KB <= 132 KB
-    if (*RS < 1) *RS = 1;
-    // one resident workgroup per CU: 256 / GY slabs, at least 32 steps of 16 rows per interleave
-    long S = 256 / *GY;
+    // one resident workgroup per CU: 256 slabs, at least 32 steps of 16 rows per interleave
+    long S = 256;
     const long max_by_rows = (M + 16L * 32 * *RS - 1) / (16L * 32 * *RS);
     if (S > max_by_rows) S = max_by_rows;
     if (S < 1) S = 1;
@@ -538,20 +527,19 @@ static int tb_plan(long long M, int N, int K, int* P, int* RS, int* KPn, int* GY
 }
 
 size_t stage_gemm_tn_bf16_stream_ws_bytes(long long M, int N, int K) {
-    int P, RS, KPn, GY; long rps;
-    const int S = tb_plan(M, N, K, &P, &RS, &KPn, &GY, &rps);
+    int P, RS, KPn; long rps;
+    const int S = tb_plan(M, N, K, &P, &RS, &KPn, &rps);
     return (size_t)S * ((size_t)N * K + N) * sizeof(float);
 }
 
 // returns 1 if the shape / alignment is not handled here, 0 on launch; *slabs = number of partials written
 int stage_gemm_tn_bf16_stream(const void* dY, const void* gate, const void* X, float* part, float* part_b, long long M, int N,
                               int K, int* slabs, void* stream) {
-    static const bool off = getenv("STAGE_GEMM_BF16_TILED") != nullptr;
-    int P, RS, KPn, GY; long rps;
-    const int S = off ? 0 : tb_plan(M, N, K, &P, &RS, &KPn, &GY, &rps);
+    int P, RS, KPn; long rps;
+    const int S = tb_plan(M, N, K, &P, &RS, &KPn, &rps);
     if (S == 0 || ((uintptr_t)dY & 3) || ((uintptr_t)X & 3) || (gate && ((uintptr_t)gate & 3))) return 1;
     typedef stage_bf16 B;
-    dim3 grid((unsigned)S, (unsigned)GY), block(64 * P * RS);
+    dim3 grid((unsigned)S), block(64 * P * RS);   // one workgroup group: gridDim.y = 1
     const size_t lds = (size_t)(RS - 1) * P * 66 * 64 * sizeof(float);
     if (lds > 64 * 1024) {
         (void)hipFuncSetAttribute((const void*)gemm_tn_bf16_stream_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -7,14 +7,14 @@
 // Every bf16 x bf16 product is exact in fp32 and v_mfma_f32_32x32x16_bf16 accumulates in fp32, so the result has
 // fp32-level accuracy (same order as the f32 MFMA chain) while a 128x128x32 block chunk costs 1536 matrix-core cycles
 // instead of 4096: every Linear / 1x1-conv of the STAGE path turns from MFMA-bound (~55 TFLOP/s fp32 in the step) into
-// an HBM-streaming kernel.  NSPLIT = 2 (three products, ~1e-5 relative) is kept for experiments (STAGE_GEMM_SPLIT=2).
+// an HBM-streaming kernel.
 // Same entry-point semantics as gemm.hip (gate = fused ReLU backward, bias / ReLU / residual epilogue, split-M
-// deterministic weight gradients); used by stage_gemm_nt / stage_gemm_tn unless STAGE_GEMM_F32 is set.
+// deterministic weight gradients); stage_gemm_nt takes this kernel for the shapes the streaming kernels decline, unless
+// STAGE_GEMM_F32 is set.  Weight gradients (TN) use the kernel below in bf16 storage mode only (NSPLIT = 1).
 //
 // LDS image: NSPLIT bf16 planes per operand, [128 rows][32 k] with an 80-byte row stride (5 x 16 B: the 16-lane service
 // groups of ds_read_b128 hit distinct 16-B slots).  The TN form (weight gradient, contraction over rows) writes the
 // planes TRANSPOSED ([column][m]) while staging, packing two consecutive rows per 32-bit LDS write.
-#include <stdlib.h>
 #include "common.h"
 #include "../../include/stage_hip.h"
 
@@ -194,12 +194,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_split_kernel(const T* __restri
         }
 }
 
-static int split_depth() {
-    static int d = -1;
-    if (d < 0) d = (getenv("STAGE_GEMM_SPLIT") && atoi(getenv("STAGE_GEMM_SPLIT")) == 2) ? 2 : 3;
-    return d;
-}
-
 extern "C" int stage_gemm_nt_bf16x3(const float* X, const float* gate, const float* W, const float* bias,
                                     const float* residual, float* Y, long long M, int N, int K, int relu,
                                     void* stream) {
@@ -209,12 +203,12 @@ extern "C" int stage_gemm_nt_bf16x3(const float* X, const float* gate, const flo
     const int vecW = (K % 4 == 0) && (((uintptr_t)W & 15) == 0);
     dim3 grid((unsigned)((M + BM - 1) / BM), (unsigned)((N + BN - 1) / BN));
     const bool fast = vecX && vecW && K >= 4;
-#define LAUNCH_NT(NS, F)                                                                                              \
-    hipLaunchKernelGGL((gemm_nt_split_kernel<NS, F>), grid, dim3(256), 0, (hipStream_t)stream, X, gate, W, bias, residual, \
-                       Y, (long)M, N, K, relu, vecX, vecW)
-    if (split_depth() == 2) { if (fast) LAUNCH_NT(2, true); else LAUNCH_NT(2, false); }
-    else { if (fast) LAUNCH_NT(3, true); else LAUNCH_NT(3, false); }
-#undef LAUNCH_NT
+    if (fast)
+        hipLaunchKernelGGL((gemm_nt_split_kernel<3, true>), grid, dim3(256), 0, (hipStream_t)stream, X, gate, W, bias, residual,
+                           Y, (long)M, N, K, relu, vecX, vecW);
+    else
+        hipLaunchKernelGGL((gemm_nt_split_kernel<3, false>), grid, dim3(256), 0, (hipStream_t)stream, X, gate, W, bias, residual,
+                           Y, (long)M, N, K, relu, vecX, vecW);
     STAGE_LAUNCH_CHECK();
     return 0;
 }
@@ -359,40 +353,6 @@ static int tn_splits_b(long long M, int N, int K) {
     if (s > TN_MAX_SPLIT) s = TN_MAX_SPLIT;
     if (s < 1) s = 1;
     return (int)s;
-}
-
-// workspace size is the same as stage_gemm_tn_ws_bytes (same split rule)
-extern "C" int stage_gemm_tn_bf16x3(const float* dY, const float* gate, const float* X, float* dW, float* db, long long M,
-                                    int N, int K, void* ws, size_t ws_bytes, void* stream) {
-    hipStream_t st = (hipStream_t)stream;
-    if (N <= 0 || K <= 0) return 0;
-    if (M <= 0) {
-        (void)hipMemsetAsync(dW, 0, sizeof(float) * (size_t)N * K, st);
-        if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * N, st);
-        return 0;
-    }
-    const int S = tn_splits_b(M, N, K);
-    if (ws_bytes < (size_t)S * ((size_t)N * K + N) * sizeof(float)) return STAGE_ERR_WORKSPACE;
-    long rps = (M + S - 1) / S;
-    rps = (rps + BK - 1) / BK * BK;
-    float* part = (float*)ws;
-    float* part_b = part + (size_t)S * N * K;
-    const int vecY = (N % 4 == 0) && (((uintptr_t)dY & 15) == 0) && (!gate || ((uintptr_t)gate & 15) == 0);
-    const int vecX = (K % 4 == 0) && (((uintptr_t)X & 15) == 0);
-    dim3 grid((N + BM - 1) / BM, (K + BN - 1) / BN, S);
-    const bool fast = vecY && vecX && N >= 4 && K >= 4;
-#define LAUNCH_TN(NS, F)                                                                                                 \
-    hipLaunchKernelGGL((gemm_tn_split_kernel<NS, F>), grid, dim3(256), 0, st, dY, gate, X, part,                          \
-                       db ? part_b : (float*)nullptr, (long)M, N, K, rps, vecY, vecX)
-    if (split_depth() == 2) { if (fast) LAUNCH_TN(2, true); else LAUNCH_TN(2, false); }
-    else { if (fast) LAUNCH_TN(3, true); else LAUNCH_TN(3, false); }
-#undef LAUNCH_TN
-    STAGE_LAUNCH_CHECK();
-    const long C = (long)N * K;
-    hipLaunchKernelGGL(slab_reduce_b_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, part, dW, S, C);
-    if (db) hipLaunchKernelGGL(slab_reduce_b_kernel, dim3((N + 255) / 256), dim3(256), 0, st, part_b, db, S, (long)N);
-    STAGE_LAUNCH_CHECK();
-    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------

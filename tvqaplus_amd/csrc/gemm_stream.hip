@@ -1,7 +1,7 @@
 // Streaming NT GEMM for the tall-skinny Linear / 1x1-conv shapes of the STAGE path (M ~ 1e5..1e6 rows, N, K ~ 128..768):
 //     Y[M,N] = epi( (X (*) gate)[M,K] . W[N,K]^T + bias )           same contract as stage_gemm_nt (gemm.hip)
-// fp32 accuracy through a two-way fp16 split with power-of-two scaling (below: STAGE_GEMM_NT_F16; the 3-way bf16 split of
-// gemm_bf16x3.hip is the other compile-time option), organised for HBM streaming:
+// fp32 accuracy through a two-way fp16 split with power-of-two scaling (below; the tiled kernel of gemm_bf16x3.hip runs the
+// 3-way bf16 split), organised for HBM streaming:
 //   * the weight tile (128 output columns x 128 k) is split ONCE per workgroup into its two fp16 planes and stays in
 //     LDS (70 KB); for K <= 128 it is never reloaded while the workgroup walks its row tiles;
 //   * the X operand never touches LDS: every wave owns 32-row tiles and loads them straight from HBM in MFMA operand
@@ -12,59 +12,21 @@
 //   * no workgroup barrier in the row loop (K <= 128): 8 waves per CU drift freely, so loads, the split VALU work, the
 //     matrix cores and the stores of different waves overlap; the next 32-k line is prefetched while one is multiplied.
 // K > 128 walks K in 128-wide chunks with a barrier pair per chunk (weight chunk reload), accumulators stay in registers.
-#include <stdlib.h>
 #include "common.h"
 #include "../../include/stage_hip.h"
 
 #ifndef GEMM_ABL
 #define GEMM_ABL 0      // developer ablation bits (timing experiments only, results wrong; 64: no row-exponent tracking): 1 one MFMA per column tile instead
-#endif                  // of 6, 2 no bf16 split (raw bits as operands), 4 X lines fetched once per wave, 8 no stores,
-                        // 16 weight fragments read from LDS for one of the four column tiles only; TN share kernel: 1, 2, 4 alike,
-                        // 32 no barrier
-#ifndef STAGE_GEMM_TERMS
-#define STAGE_GEMM_TERMS 3      // bf16 mode only (STAGE_GEMM_NT_F16 / _TN_F16 = 0): bf16 terms per fp32 operand: 3 = exact split (six products, 3e-7 vs fp64);
-#endif                          // 2 = hi + mid only (three products kept: every product carries a relative error <= ~2^-17,
-                                // measured ~1e-5 of the result's scale; half the matrix-core work) -- `make TERMS=2`
+#endif                  // of 3, 2 no fp16 split (raw bits as operands), 4 X lines fetched once per wave, 8 no stores,
+                        // 16 weight fragments read from LDS for one of the four column tiles only; TN kernels: 4 alike
 #define SBN 128                 // output columns per workgroup
 #define SKC 128                 // k per resident weight chunk
-#define SWS (SKC + 8)           // bf16 per LDS row of a plane (272 B: 16-lane ds_read_b128 groups hit distinct slots)
-#define SPLANE (SBN * SWS)      // bf16 elements per plane
+#define SWS (SKC + 8)           // fp16 per LDS row of a plane (272 B: 16-lane ds_read_b128 groups hit distinct slots)
+#define SPLANE (SBN * SWS)      // fp16 elements per plane
 #define SWAVES 8
 
-typedef __bf16 sbf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ unsigned s_cvt_pk_bf16(float lo, float hi) {
-    unsigned r;
-    asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-    return r;
-}
-// (a, b) -> three packed bf16 pairs (a low half): exact residual splits, a == a1 + a2 + a3
-__device__ __forceinline__ void s_split3(float a, float b, unsigned (&out)[3]) {
-#pragma unroll
-    for (int s = 0; s < 3; s++) {
-        if (s < STAGE_GEMM_TERMS) {
-            out[s] = s_cvt_pk_bf16(a, b);
-            if (s + 1 < STAGE_GEMM_TERMS) {
-                a -= __uint_as_float(out[s] << 16);
-                b -= __uint_as_float(out[s] & 0xFFFF0000u);
-            }
-        } else out[s] = 0u;
-    }
-}
-// acc += sum of the kept cross terms of (a0 + a1 + a2) x (b0 + b1 + b2), smallest first
-__device__ __forceinline__ f32x16 s_mfma_terms(const sbf16x8 (&a)[3], const sbf16x8 (&b)[3], f32x16 acc) {
-    if (STAGE_GEMM_TERMS == 3) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], acc, 0, 0, 0);
-    }
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], acc, 0, 0, 0);
-    return acc;
-}
 // ---------------------------------------------------------------------------------------------------------------------
-// NT kernel: fp32 products as a TWO-way fp16 split (STAGE_GEMM_NT_F16, default).  fp16 carries 11 significant bits, so
+// NT kernel: fp32 products as a TWO-way fp16 split.  fp16 carries 11 significant bits, so
 // x = hi + lo (both round-to-nearest) holds 22-23 bits of x and the three products hi*hi + hi*lo + lo*hi reproduce the fp32
 // product to ~2^-22 -- against an fp64 product the result's error is BELOW that of a plain fp32 FMA chain (numpy emulation,
 // K = 384, relative to the result's rms: max 1.2e-6 / rms 2.1e-7; torch / numpy fp32 matmul 3.8e-6 / 3.5e-7) -- with HALF the
@@ -76,9 +38,6 @@ __device__ __forceinline__ f32x16 s_mfma_terms(const sbf16x8 (&a)[3], const sbf1
 //   * W: one exponent per workgroup from a pre-pass over its (<= 128 x K) weight tile.
 // An element far below its row's maximum keeps an ABSOLUTE error of 2^-26 of that maximum (fp16 denormals) instead of
 // fp32's relative 2^-24: irrelevant for a dot product, whose error scale is the largest terms.
-#ifndef STAGE_GEMM_NT_F16
-#define STAGE_GEMM_NT_F16 1
-#endif
 __device__ __forceinline__ f32x16 h_mfma_terms(const sf16x8 (&a)[2], const sf16x8 (&b)[2], f32x16 acc) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[1], b[0], acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0], b[1], acc, 0, 0, 0);
@@ -88,9 +47,6 @@ __device__ __forceinline__ f32x16 h_mfma_terms(const sf16x8 (&a)[2], const sf16x
 // TN kernels (contraction over rows): the scale belongs to an operand COLUMN = a lane of the tile's producer.  Running
 // exponent of the column (both lane halves agree); returns the change of the scale's exponent field at this step (<= 0),
 // which the consumers of the tile apply to their accumulators before they use it.
-#ifndef STAGE_GEMM_TN_F16
-#define STAGE_GEMM_TN_F16 1
-#endif
 __device__ __forceinline__ float h_amax8(const float (&v)[8]) {
     return h_amax3(h_amax3(h_amax3(h_amax3(v[0], v[1], v[2]), v[3], v[4]), v[5], v[6]), v[7], v[7]);
 }
@@ -162,7 +118,7 @@ __global__ __launch_bounds__(64 * SWAVES, 2) void gemm_nt_stream_kernel(const fl
                                                                         unsigned* __restrict__ mask_out, long M, int N,
                                                                         int K, int relu, int xcd_gx, StageColsum cs = StageColsum()) {
     constexpr bool HAS_GATE = GATE == 1;
-    extern __shared__ __attribute__((aligned(16))) unsigned short Wp[];   // [2 fp16 planes (3 bf16 planes)][SBN][SWS], k permuted per 16-group
+    extern __shared__ __attribute__((aligned(16))) unsigned short Wp[];   // [2 fp16 planes][SBN][SWS], k permuted per 16-group
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     // Workgroup -> (row group bx, column tile by).  Workgroups are dealt round-robin to the 8 XCDs (id % 8), each with its own
@@ -184,40 +140,29 @@ __global__ __launch_bounds__(64 * SWAVES, 2) void gemm_nt_stream_kernel(const fl
 
     // weight chunk kc -> LDS planes.  float4 group q of a row covers k = 4q..4q+3 = 16u + 8c + 4h' + e  (q = 4u + 2c + h')
     // and lands at plane position 16u + 8h' + 4c + e, i.e. lane-half h' finds its 8 operand values contiguous.
-    // fp16 mode: power-of-two scale of this workgroup's weight tile (all K), from a pre-pass over its rows (L2 reads)
-    int w_up = 127;                                      // exponent field of the scale; 127 = 1.0
-    if (STAGE_GEMM_NT_F16) {
-        float wm = 0.f;
-        const int kq = K >> 2;
-        for (int e = tid; e < SBN * kq; e += 64 * SWAVES) {
-            const int n = e / kq, q = e - n * kq;
-            wm = s_absmax4(wm, s_load4(W, n0 + n, K, 4 * q, N, K));
-        }
-        wm = wave_max(wm);
-        float* red = reinterpret_cast<float*>(Wp);
-        if (lane == 0) red[wave] = wm;
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < SWAVES; i++) wm = fmaxf(wm, red[i]);
-        __syncthreads();                                 // the planes are written next
-        w_up = h_up_field((int)(__float_as_uint(wm) >> 23) & 0xff);
+    // power-of-two scale of this workgroup's weight tile (all K), from a pre-pass over its rows (L2 reads)
+    float wm = 0.f;
+    const int kq = K >> 2;
+    for (int e = tid; e < SBN * kq; e += 64 * SWAVES) {
+        const int n = e / kq, q = e - n * kq;
+        wm = s_absmax4(wm, s_load4(W, n0 + n, K, 4 * q, N, K));
     }
+    wm = wave_max(wm);
+    float* red = reinterpret_cast<float*>(Wp);
+    if (lane == 0) red[wave] = wm;
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < SWAVES; i++) wm = fmaxf(wm, red[i]);
+    __syncthreads();                                     // the planes are written next
+    const int w_up = h_up_field((int)(__float_as_uint(wm) >> 23) & 0xff);   // exponent field of the scale; 127 = 1.0
     const float w_sc = __uint_as_float((unsigned)w_up << 23);
     auto put_w = [&](float4 v, int n, int q) {
         const int pos = 16 * (q >> 2) + 8 * (q & 1) + 4 * ((q >> 1) & 1);
-        if (STAGE_GEMM_NT_F16) {
-            unsigned h01, l01, h23, l23;
-            h_split2(v.x, v.y, w_sc, h01, l01);
-            h_split2(v.z, v.w, w_sc, h23, l23);
-            *reinterpret_cast<uint2*>(&Wp[n * SWS + pos]) = make_uint2(h01, h23);
-            *reinterpret_cast<uint2*>(&Wp[SPLANE + n * SWS + pos]) = make_uint2(l01, l23);
-        } else {
-            unsigned s01[3], s23[3];
-            s_split3(v.x, v.y, s01);
-            s_split3(v.z, v.w, s23);
-#pragma unroll
-            for (int s = 0; s < STAGE_GEMM_TERMS; s++) *reinterpret_cast<uint2*>(&Wp[s * SPLANE + n * SWS + pos]) = make_uint2(s01[s], s23[s]);
-        }
+        unsigned h01, l01, h23, l23;
+        h_split2(v.x, v.y, w_sc, h01, l01);
+        h_split2(v.z, v.w, w_sc, h23, l23);
+        *reinterpret_cast<uint2*>(&Wp[n * SWS + pos]) = make_uint2(h01, h23);
+        *reinterpret_cast<uint2*>(&Wp[SPLANE + n * SWS + pos]) = make_uint2(l01, l23);
     };
     auto load_w = [&](int kc) {
         for (int e = tid; e < SBN * (SKC / 4); e += 64 * SWAVES) {
@@ -345,7 +290,7 @@ __global__ __launch_bounds__(64 * SWAVES, 2) void gemm_nt_stream_kernel(const fl
         for (int nt = 0; nt < 4; nt++)
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[nt][r] = 0.f;
-        int xeb = 0;                                     // fp16 mode: biased exponent of this lane's row maximum so far
+        int xeb = 0;                                     // biased exponent of this lane's row maximum so far
 
         for (int kc = 0; kc < nkc; kc++) {
             const int kb = kc * SKC;
@@ -398,7 +343,7 @@ __global__ __launch_bounds__(64 * SWAVES, 2) void gemm_nt_stream_kernel(const fl
                     vv[2 * up + 1] = v1;
                 }
                 float x_sc = 1.f;
-                if (STAGE_GEMM_NT_F16 && !(GEMM_ABL & 64)) {
+                if (!(GEMM_ABL & 64)) {
                     // the row's exponent: largest magnitude of the line (both lane halves), raised only when a value would
                     // pass 2^15 after scaling; the first line of a tile sets it (the accumulators are zero)
                     const float m = xmax32(s_absmax4(s_absmax4(s_absmax4(s_absmax4(0.f, vv[0]), vv[1]), vv[2]), vv[3]));
@@ -421,63 +366,30 @@ __global__ __launch_bounds__(64 * SWAVES, 2) void gemm_nt_stream_kernel(const fl
                 for (int up = 0; up < 2; up++) {
                     const float4 v0 = vv[2 * up], v1 = vv[2 * up + 1];
                     const int koff = 16 * (2 * L + up) + 8 * h;
-                    if (STAGE_GEMM_NT_F16) {
-                        unsigned ph[4], pl[4];
-                        sf16x8 a[2], b[2];
-                        if (GEMM_ABL & 2) {
-                            a[0] = __builtin_bit_cast(sf16x8, v0);
-                            a[1] = __builtin_bit_cast(sf16x8, v1);
-                        } else {
-                            h_split2(v0.x, v0.y, x_sc, ph[0], pl[0]);
-                            h_split2(v0.z, v0.w, x_sc, ph[1], pl[1]);
-                            h_split2(v1.x, v1.y, x_sc, ph[2], pl[2]);
-                            h_split2(v1.z, v1.w, x_sc, ph[3], pl[3]);
-                            a[0] = __builtin_bit_cast(sf16x8, make_uint4(ph[0], ph[1], ph[2], ph[3]));
-                            a[1] = __builtin_bit_cast(sf16x8, make_uint4(pl[0], pl[1], pl[2], pl[3]));
-                        }
-#pragma unroll
-                        for (int nt = 0; nt < 4; nt++) {
-#pragma unroll
-                            for (int s2 = 0; s2 < 2; s2++)
-                                if (!(GEMM_ABL & 16) || nt == 0)
-                                    b[s2] = __builtin_bit_cast(sf16x8, *reinterpret_cast<const uint4*>(&Wp[s2 * SPLANE + (nt * 32 + l31) * SWS + koff]));
-                            if (GEMM_ABL & 1) {
-                                acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0] + a[1], b[0] + b[1], acc[nt], 0, 0, 0);
-                                continue;
-                            }
-                            acc[nt] = h_mfma_terms(a, b, acc[nt]);
-                        }
-                        continue;
-                    }
-                    unsigned p0[3], p1[3], p2[3], p3[3];
-                    sbf16x8 a[3];
+                    unsigned ph[4], pl[4];
+                    sf16x8 a[2], b[2];
                     if (GEMM_ABL & 2) {
-                        a[0] = __builtin_bit_cast(sbf16x8, v0);
-                        a[1] = __builtin_bit_cast(sbf16x8, v1);
-                        a[2] = __builtin_bit_cast(sbf16x8, make_float4(v0.x, v1.y, v0.z, v1.w));
+                        a[0] = __builtin_bit_cast(sf16x8, v0);
+                        a[1] = __builtin_bit_cast(sf16x8, v1);
                     } else {
-                        s_split3(v0.x, v0.y, p0);
-                        s_split3(v0.z, v0.w, p1);
-                        s_split3(v1.x, v1.y, p2);
-                        s_split3(v1.z, v1.w, p3);
-#pragma unroll
-                        for (int s = 0; s < STAGE_GEMM_TERMS; s++) a[s] = __builtin_bit_cast(sbf16x8, make_uint4(p0[s], p1[s], p2[s], p3[s]));
+                        h_split2(v0.x, v0.y, x_sc, ph[0], pl[0]);
+                        h_split2(v0.z, v0.w, x_sc, ph[1], pl[1]);
+                        h_split2(v1.x, v1.y, x_sc, ph[2], pl[2]);
+                        h_split2(v1.z, v1.w, x_sc, ph[3], pl[3]);
+                        a[0] = __builtin_bit_cast(sf16x8, make_uint4(ph[0], ph[1], ph[2], ph[3]));
+                        a[1] = __builtin_bit_cast(sf16x8, make_uint4(pl[0], pl[1], pl[2], pl[3]));
                     }
-                    sbf16x8 b[3];
 #pragma unroll
                     for (int nt = 0; nt < 4; nt++) {
 #pragma unroll
-                        for (int s = 0; s < STAGE_GEMM_TERMS; s++)
-                            if (!(GEMM_ABL & 16) || nt == 0)   // ablation: weight fragments read for the first column tile only
-                                b[s] = __builtin_bit_cast(sbf16x8, *reinterpret_cast<const uint4*>(&Wp[s * SPLANE + (nt * 32 + l31) * SWS + koff]));
-                        // kept cross terms, smallest first
+                        for (int s2 = 0; s2 < 2; s2++)
+                            if (!(GEMM_ABL & 16) || nt == 0)
+                                b[s2] = __builtin_bit_cast(sf16x8, *reinterpret_cast<const uint4*>(&Wp[s2 * SPLANE + (nt * 32 + l31) * SWS + koff]));
                         if (GEMM_ABL & 1) {
-                            const sbf16x8 am = __builtin_bit_cast(sbf16x8, __builtin_bit_cast(uint4, a[0]) ^ __builtin_bit_cast(uint4, a[1]) ^ __builtin_bit_cast(uint4, a[2]));
-                            const sbf16x8 bm = __builtin_bit_cast(sbf16x8, __builtin_bit_cast(uint4, b[0]) ^ __builtin_bit_cast(uint4, b[1]) ^ __builtin_bit_cast(uint4, b[2]));
-                            acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[nt], 0, 0, 0);
+                            acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[0] + a[1], b[0] + b[1], acc[nt], 0, 0, 0);
                             continue;
                         }
-                        acc[nt] = s_mfma_terms(a, b, acc[nt]);
+                        acc[nt] = h_mfma_terms(a, b, acc[nt]);
                     }
                 }
             };
@@ -521,14 +433,12 @@ __global__ __launch_bounds__(64 * SWAVES, 2) void gemm_nt_stream_kernel(const fl
         // Straight-line stores: a residual load or a per-row guard inside this loop makes the compiler put an
         // s_waitcnt vmcnt(0) in front of every store (each store then waits for the previous one to be acknowledged).
         const bool full = t * 32 + 32 <= M;
-        if (STAGE_GEMM_NT_F16) {                          // back to true units: 2^-(row scale + weight scale), per output row
-            const int dn = 254 - h_up_field(xeb) - w_up;
+        const int dn = 254 - h_up_field(xeb) - w_up;      // back to true units: 2^-(row scale + weight scale), per output row
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int dr = __builtin_amdgcn_ds_bpermute(4 * ((r & 3) + 8 * (r >> 2) + 4 * h), dn);
+        for (int r = 0; r < 16; r++) {
+            const int dr = __builtin_amdgcn_ds_bpermute(4 * ((r & 3) + 8 * (r >> 2) + 4 * h), dn);
 #pragma unroll
-                for (int nt = 0; nt < 4; nt++) acc[nt][r] = __builtin_ldexpf(acc[nt][r], dr);
-            }
+            for (int nt = 0; nt < 4; nt++) acc[nt][r] = __builtin_ldexpf(acc[nt][r], dr);
         }
         if (COLSUM) {
             // rows of this lane: t*32 + 4h + dm(r); column n0 + nt*32 + l31 = bit l31 of keep word (n0 >> 5) + nt of the row
@@ -634,21 +544,11 @@ int stage_gemm_nt_stream(const float* X, const void* gate, int gate_kind, const 
                          const float* residual, float* Y, unsigned* mask_out, long long M, int N, int K, int relu,
                          void* stream) {
     if (!gate) gate_kind = 0;
-    {   // developer bisect switch: STAGE_GEMM_STREAM_SKIP="n384" / "k300" / "g2" (gate kind) / "r" (residual) / "m" (mask out)
-        static const char* skip = getenv("STAGE_GEMM_STREAM_SKIP");
-        if (skip) {
-            const int v = atoi(skip + 1);
-            if ((skip[0] == 'n' && v == N) || (skip[0] == 'k' && v == K) || (skip[0] == 'g' && v == gate_kind) ||
-                (skip[0] == 'r' && residual) || (skip[0] == 'm' && mask_out))
-                return 1;
-        }
-    }
     const bool vec = (K % 4 == 0) && K >= 4 && (((uintptr_t)X & 15) == 0) && (((uintptr_t)W & 15) == 0) &&
                      (gate_kind != 1 || ((uintptr_t)gate & 15) == 0);
     // rows: from 4096; from 1024 for K <= 384, where a handful of workgroups with one 32-row tile per wave still beat the
     // tiled kernel's 128 x 128 tiles (M = 3200: 20 -> 12 us at K = 128, 35 -> 26 us at K = 384, but 64 -> 80 us at K = 768)
-    static const long long min_m_env = getenv("STAGE_GEMM_STREAM_MIN_M") ? atoll(getenv("STAGE_GEMM_STREAM_MIN_M")) : 0;
-    const long long min_m_nt = min_m_env ? min_m_env : (K <= 384 ? 1024 : 4096);
+    const long long min_m_nt = K <= 384 ? 1024 : 4096;
     if (!vec || M < min_m_nt || K < 64 || M * (long long)K * 4 >= (1ll << 31)) return 1;   // buffer addressing: < 2 GiB
     if ((gate_kind == 2 || mask_out) && residual) return 1;                              // combinations nobody needs
     if (mask_out && gate_kind != 0) return 1;
@@ -659,9 +559,8 @@ int stage_gemm_nt_stream(const float* X, const void* gate, int gate_kind, const 
     if (gx < 1) gx = 1;                                   // range run side by side
     if (gx > n_bt) gx = n_bt;
     // several column tiles and at least 8 row groups: XCD-aware 1-D grid (kernel comment), gx rounded down to a multiple of 8
-    static const bool no_xcd = getenv("STAGE_GEMM_NO_XCD") != nullptr;
     int xcd_gx = 0;
-    if (n_tiles > 1 && gx >= 8 && !no_xcd) {
+    if (n_tiles > 1 && gx >= 8) {
         gx = gx / 8 * 8;
         xcd_gx = (int)gx;
     }
@@ -704,7 +603,7 @@ int stage_gemm_nt_stream_lnparam(const float* dY, const unsigned* gate_mask, con
                                  const float* rstd, const unsigned* keep_mask, float p_drop, float* dgamma, float* dbeta,
                                  long long M, int N, int K, void* ws, size_t ws_bytes, void* stream) {
     const bool vec = (K % 4 == 0) && K >= 4 && (((uintptr_t)dY & 15) == 0) && (((uintptr_t)Wt & 15) == 0);
-    if (!STAGE_GEMM_NT_F16 || !vec || M < 4096 || K < 64 || N % 4 != 0 || M * (long long)K * 4 >= (1ll << 31) ||
+    if (!vec || M < 4096 || K < 64 || N % 4 != 0 || M * (long long)K * 4 >= (1ll << 31) ||
         M * (long long)N * 4 >= (1ll << 31))
         return 1;
     if (ws_bytes < stage_gemm_nt_lnparam_ws(M, N)) return STAGE_ERR_WORKSPACE;
@@ -760,181 +659,15 @@ int stage_gemm_nt_stream_lnparam(const float* dY, const unsigned* gate_mask, con
 // lines, 4x more VMEM instructions than dwordx4 but no LDS, no barrier, no transpose.  The loads are buffer loads
 // (resource + wave-uniform row offset in an SGPR + constant 32-bit lane offset): no 64-bit per-lane address arithmetic
 // in the loop, and rows past the end of the tensor read as 0.  Each wave owns a 64 x 64 patch of the 128 x 128 output tile
-// of its workgroup (2 x 2 MFMA tiles; this variant without operand sharing still runs the 3-way bf16 split) and walks the rows of its slab
-// 16 at a time with the next step's 32 (48 with gate) loads in flight.
+// of its workgroup (2 x 2 MFMA tiles) and walks the rows of its slab 16 at a time with the next step's loads in flight.
 // =====================================================================================================================
 __device__ __forceinline__ float s_buf_load(__amdgpu_buffer_rsrc_t r, int voff_bytes, int soff_bytes) {
     return __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(r, voff_bytes, soff_bytes, 0));
 }
 
-template <int GATE>   // 0 none, 1 fp32 gate (same layout as dY), 2 bit mask (uint32 [ceil(N/32)][M], word-major)
-__global__ __launch_bounds__(256, 2) void gemm_tn_stream_kernel(const float* __restrict__ dY, const float* __restrict__ G,
-                                                                const float* __restrict__ X, float* __restrict__ part,
-                                                                float* __restrict__ part_b, long M, int N, int K,
-                                                                long rows_per_split) {
-    // Two step buffers (loads one step ahead).  A third buffer / loads two steps ahead measured no faster (0.283 vs 0.284 ms
-    // at 960000 x 128 x 128), i.e. this kernel is not bound by the latency of its dword loads.
-    constexpr int NBUF = 2;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int l31 = lane & 31, h = lane >> 5;
-    const int pn = wave >> 1, pk = wave & 1;
-    const int n_base = blockIdx.x * 128 + pn * 64, k_base = blockIdx.y * 128 + pk * 64;
-    const int split = blockIdx.z;
-    const long mbeg = (long)split * rows_per_split;
-    const long mend = min(M, mbeg + rows_per_split);
-    const int NWN = (N + 31) >> 5;                        // mask words per row
-    const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc((void*)dY, 0, (int)(M * N * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)X, 0, (int)(M * K * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(GATE != 0 ? G : dY), 0, GATE == 2 ? (int)(M * NWN * 4) : (int)(M * N * 4), 0x00020000);
-    // this lane's two dY columns and two X columns (clamped for the address, zeroed by the flag) as byte offsets inside
-    // a 16-row step
-    int yoff[2], xoff[2], gbit[2];
-    bool nok[2], kok[2];
-#pragma unroll
-    for (int t = 0; t < 2; t++) {
-        const int n = n_base + 32 * t + l31, k = k_base + 32 * t + l31;
-        nok[t] = n < N;
-        kok[t] = k < K;
-        const int nc = nok[t] ? n : N - 1;
-        yoff[t] = (8 * h * N + nc) * 4;
-        xoff[t] = (8 * h * K + (kok[t] ? k : K - 1)) * 4;
-        gbit[t] = nc & 31;
-    }
-    // GATE 2: byte offset of this lane's mask word column (word-major mask: [word][row]) for its row half
-    int moff[2];
-#pragma unroll
-    for (int t = 0; t < 2; t++) moff[t] = (int)(((long)min((n_base >> 5) + t, NWN - 1) * M + 8 * h) * 4);
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
-    float bsum[2] = {0.f, 0.f};
-
-    float ya[NBUF][2][8], xa[NBUF][2][8], ga[GATE != 0 ? NBUF : 1][2][8];   // [buffer][tile][row]; GATE 2: mask words
-    auto fetch = [&](int buf, long m0) {
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const int sy = (int)((m0 + r) * N * 4), sx = (int)((m0 + r) * K * 4);   // wave-uniform row offsets (bytes)
-#pragma unroll
-            for (int t = 0; t < 2; t++) {
-                ya[buf][t][r] = s_buf_load(ry, yoff[t], sy);
-                xa[buf][t][r] = s_buf_load(rx, xoff[t], sx);
-                if (GATE == 1) ga[buf][t][r] = s_buf_load(rg, yoff[t], sy);
-                if (GATE == 2) ga[buf][t][r] = s_buf_load(rg, moff[t], (int)((m0 + r) * 4));   // rows past the end read 0
-            }
-        }
-    };
-    // The SIMD issues one instruction at a time and only ~5-7 of them hide behind each MFMA: at ~17 non-MFMA instructions
-    // per MFMA this kernel is issue-bound, so the steady state (full 16-row step, all four column tiles inside the matrix)
-    // drops the per-element validity selects, and only the waves that emit the bias gradient keep its running sums.
-    const bool cols_in = nok[0] && nok[1] && kok[0] && kok[1];           // lane-level, but false only in edge tiles
-    const bool want_b = part_b != nullptr && blockIdx.y == 0 && pk == 0;
-    auto step = [&](int buf, long m0) {
-        const bool full = m0 + 16 <= mend;
-        const bool fast = full && __all(cols_in);
-        sbf16x8 a[2][3], b[2][3];
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            float yv[8], xv[8];
-#pragma unroll
-            for (int r = 0; r < 8; r++) {
-                float y = ya[buf][t][r];
-                if (GATE == 1) y = ga[buf][t][r] > 0.f ? y : 0.f;
-                if (GATE == 2) y = ((__float_as_uint(ga[buf][t][r]) >> gbit[t]) & 1u) ? y : 0.f;
-                yv[r] = y;
-                xv[r] = xa[buf][t][r];
-            }
-            if (!fast) {   // one uniform branch per tile, straight-line selects inside
-#pragma unroll
-                for (int r = 0; r < 8; r++) {
-                    const bool rok = full || (m0 + 8 * h + r < mend);   // rows of the next slab / past the end contribute 0
-                    yv[r] = (rok && nok[t]) ? yv[r] : 0.f;
-                    xv[r] = (rok && kok[t]) ? xv[r] : 0.f;
-                }
-            }
-            if (want_b) {
-#pragma unroll
-                for (int r = 0; r < 8; r++) bsum[t] += yv[r];
-            }
-            unsigned p[4][3], q[4][3];
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                s_split3(yv[2 * i], yv[2 * i + 1], p[i]);
-                s_split3(xv[2 * i], xv[2 * i + 1], q[i]);
-            }
-#pragma unroll
-            for (int s = 0; s < STAGE_GEMM_TERMS; s++) {
-                a[t][s] = __builtin_bit_cast(sbf16x8, make_uint4(p[0][s], p[1][s], p[2][s], p[3][s]));
-                b[t][s] = __builtin_bit_cast(sbf16x8, make_uint4(q[0][s], q[1][s], q[2][s], q[3][s]));
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                // kept cross terms, smallest first
-                acc[i][j] = s_mfma_terms(a[i], b[j], acc[i][j]);
-            }
-    };
-    if (mbeg < mend) {
-        if (NBUF == 2) {
-            fetch(0, mbeg);
-            for (long m0 = mbeg; m0 < mend; m0 += 32) {
-                if (m0 + 16 < mend) fetch(1, m0 + 16);
-                step(0, m0);
-                if (m0 + 16 < mend) {
-                    if (m0 + 32 < mend) fetch(0, m0 + 32);
-                    step(1, m0 + 16);
-                }
-            }
-        } else {
-            // loads two steps ahead (rows past the slab are masked in step, rows past the tensor read 0)
-            fetch(0, mbeg);
-            fetch(1, mbeg + 16);
-            for (long m0 = mbeg; m0 < mend; m0 += 48) {
-                fetch(2 % NBUF, m0 + 32);
-                step(0, m0);
-                if (m0 + 16 < mend) {
-                    fetch(0, m0 + 48);
-                    step(1, m0 + 16);
-                }
-                if (m0 + 32 < mend) {
-                    fetch(1, m0 + 64);
-                    step(2 % NBUF, m0 + 32);
-                }
-            }
-        }
-    }
-    // C/D layout of the 32x32 MFMA: col = lane & 31 (k), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (n)
-    float* po = part + (size_t)split * N * K;
-#pragma unroll
-    for (int i = 0; i < 2; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int k = k_base + 32 * j + l31;
-            if (k >= K) continue;
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int n = n_base + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * h;
-                if (n < N) po[(size_t)n * K + k] = acc[i][j][r];
-            }
-        }
-    if (want_b) {
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            const float s = xsum32(bsum[t], bsum[t]);
-            const int n = n_base + 32 * t + l31;
-            if (h == 0 && n < N) part_b[(size_t)split * N + n] = s;
-        }
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Same patch layout, but every 32-column operand tile is loaded, gated and split by ONE wave and handed to the wave that
+// GATE: 0 none, 1 fp32 gate (same layout as dY), 2 bit mask (uint32 [ceil(N/32)][M], word-major).
+// Every 32-column operand tile is loaded, gated and split by ONE wave and handed to the wave that
 // shares it through LDS: wave (pn, pk) prepares dY tile pk of its row patch (shared with wave (pn, 1 - pk)) and X tile pn
 // of its column patch (shared with wave (1 - pn, pk)).  Matrix-core and VALU time of a SIMD add (DESIGN.md finding 13),
 // and this kernel spent ~480 VALU cycles per step next to 768 MFMA cycles on work that was done twice: per wave and step
@@ -947,9 +680,9 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_share_kernel(const float* __re
                                                                const float* __restrict__ X, float* __restrict__ part,
                                                                float* __restrict__ part_b, long M, int N, int K,
                                                                long rows_per_split) {
-    __shared__ uint4 ex[2][4][6][64];                     // [buffer][wave][3 dY planes, 3 X planes][lane]  (48 KB)
-    __shared__ int exd[2][4][2][64];                      // fp16 mode: exponent change of the dY / X tile column at this step
-    int eby = 0, ebx = 0;                                 // fp16 mode: running exponents of the columns this lane prepares
+    __shared__ uint4 ex[2][4][6][64];                     // [buffer][wave][dY hi, lo, -, X hi, lo, -][lane]  (48 KB; slots 2 and 5 unused)
+    __shared__ int exd[2][4][2][64];                      // exponent change of the dY / X tile column at this step
+    int eby = 0, ebx = 0;                                 // running exponents of the columns this lane prepares
     int upA[2] = {254, 254}, upB[2] = {254, 254};         // and the scale fields in force for the tiles this wave consumes
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int l31 = lane & 31, h = lane >> 5;
@@ -1017,89 +750,46 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_share_kernel(const float* __re
 #pragma unroll
             for (int r = 0; r < 8; r++) bsum += yv[r];
         }
-        if (STAGE_GEMM_TN_F16) {
-            const int dy_ = h_track8(yv, eby), dx_ = h_track8(xv, ebx);
-            uint4 yh, yl, xh, xl;
-            h_split8(yv, eby, yh, yl);
-            h_split8(xv, ebx, xh, xl);
-            ex[xb][wave][0][lane] = yh;
-            ex[xb][wave][1][lane] = yl;
-            ex[xb][wave][3][lane] = xh;
-            ex[xb][wave][4][lane] = xl;
-            exd[xb][wave][0][lane] = dy_;
-            exd[xb][wave][1][lane] = dx_;
-            __syncthreads();
-            sf16x8 a[2][2], b[2][2];
-            int dA[2], dB[2];
+        const int dy_ = h_track8(yv, eby), dx_ = h_track8(xv, ebx);
+        uint4 yh, yl, xh, xl;
+        h_split8(yv, eby, yh, yl);
+        h_split8(xv, ebx, xh, xl);
+        ex[xb][wave][0][lane] = yh;
+        ex[xb][wave][1][lane] = yl;
+        ex[xb][wave][3][lane] = xh;
+        ex[xb][wave][4][lane] = xl;
+        exd[xb][wave][0][lane] = dy_;
+        exd[xb][wave][1][lane] = dx_;
+        __syncthreads();
+        sf16x8 a[2][2], b[2][2];
+        int dA[2], dB[2];
 #pragma unroll
-            for (int t = 0; t < 2; t++) {
+        for (int t = 0; t < 2; t++) {
 #pragma unroll
-                for (int s2 = 0; s2 < 2; s2++) {
-                    a[t][s2] = __builtin_bit_cast(sf16x8, ex[xb][pn * 2 + t][s2][lane]);
-                    b[t][s2] = __builtin_bit_cast(sf16x8, ex[xb][t * 2 + pk][3 + s2][lane]);
+            for (int s2 = 0; s2 < 2; s2++) {
+                a[t][s2] = __builtin_bit_cast(sf16x8, ex[xb][pn * 2 + t][s2][lane]);
+                b[t][s2] = __builtin_bit_cast(sf16x8, ex[xb][t * 2 + pk][3 + s2][lane]);
+            }
+            dA[t] = exd[xb][pn * 2 + t][0][lane];
+            dB[t] = exd[xb][t * 2 + pk][1][lane];
+        }
+        if (__any((dA[0] | dA[1] | dB[0] | dB[1]) != 0)) {   // a column's scale moved: bring the accumulators along
+#pragma unroll
+            for (int i = 0; i < 2; i++) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int dr = __builtin_amdgcn_ds_bpermute(4 * h_row_of(r, h), dA[i]);
+#pragma unroll
+                    for (int j = 0; j < 2; j++) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], dr + dB[j]);
                 }
-                dA[t] = exd[xb][pn * 2 + t][0][lane];
-                dB[t] = exd[xb][t * 2 + pk][1][lane];
+                upA[i] += dA[i];
+                upB[i] += dB[i];
             }
-            if (__any((dA[0] | dA[1] | dB[0] | dB[1]) != 0)) {   // a column's scale moved: bring the accumulators along
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int dr = __builtin_amdgcn_ds_bpermute(4 * h_row_of(r, h), dA[i]);
-#pragma unroll
-                        for (int j = 0; j < 2; j++) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], dr + dB[j]);
-                    }
-                    upA[i] += dA[i];
-                    upB[i] += dB[i];
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 2; i++)
-#pragma unroll
-                for (int j = 0; j < 2; j++) acc[i][j] = h_mfma_terms(a[i], b[j], acc[i][j]);
-            return;
         }
-        unsigned p[4][3], q[4][3];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            if (GEMM_ABL & 2) {
-                p[i][0] = __float_as_uint(yv[2 * i]); p[i][1] = __float_as_uint(yv[2 * i + 1]); p[i][2] = p[i][0] ^ p[i][1];
-                q[i][0] = __float_as_uint(xv[2 * i]); q[i][1] = __float_as_uint(xv[2 * i + 1]); q[i][2] = q[i][0] ^ q[i][1];
-                continue;
-            }
-            s_split3(yv[2 * i], yv[2 * i + 1], p[i]);
-            s_split3(xv[2 * i], xv[2 * i + 1], q[i]);
-        }
-#pragma unroll
-        for (int s = 0; s < STAGE_GEMM_TERMS; s++) {
-            ex[xb][wave][s][lane] = make_uint4(p[0][s], p[1][s], p[2][s], p[3][s]);
-            ex[xb][wave][3 + s][lane] = make_uint4(q[0][s], q[1][s], q[2][s], q[3][s]);
-        }
-        if (!(GEMM_ABL & 32)) __syncthreads();
-        // dY tile t of this row patch was prepared by wave (pn, t), X tile t of this column patch by wave (t, pk); the own
-        // fragments are read back as well: a register array indexed by the wave's pk / pn would live in scratch
-        sbf16x8 a[2][3], b[2][3];
-#pragma unroll
-        for (int t = 0; t < 2; t++)
-#pragma unroll
-            for (int s = 0; s < STAGE_GEMM_TERMS; s++) {
-                a[t][s] = __builtin_bit_cast(sbf16x8, ex[xb][pn * 2 + t][s][lane]);
-                b[t][s] = __builtin_bit_cast(sbf16x8, ex[xb][t * 2 + pk][3 + s][lane]);
-            }
 #pragma unroll
         for (int i = 0; i < 2; i++)
 #pragma unroll
-            for (int j = 0; j < 2; j++) {
-                if (GEMM_ABL & 1) {
-                    const sbf16x8 am = __builtin_bit_cast(sbf16x8, __builtin_bit_cast(uint4, a[i][0]) ^ __builtin_bit_cast(uint4, a[i][1]) ^ __builtin_bit_cast(uint4, a[i][2]));
-                    const sbf16x8 bm = __builtin_bit_cast(sbf16x8, __builtin_bit_cast(uint4, b[j][0]) ^ __builtin_bit_cast(uint4, b[j][1]) ^ __builtin_bit_cast(uint4, b[j][2]));
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, acc[i][j], 0, 0, 0);
-                    continue;
-                }
-                // kept cross terms, smallest first
-                acc[i][j] = s_mfma_terms(a[i], b[j], acc[i][j]);
-            }
+            for (int j = 0; j < 2; j++) acc[i][j] = h_mfma_terms(a[i], b[j], acc[i][j]);
     };
     // the loop bounds are workgroup-uniform (every wave of a workgroup walks the same slab), so the barriers match
     if (mbeg < mend) {
@@ -1113,16 +803,15 @@ __global__ __launch_bounds__(256, 2) void gemm_tn_share_kernel(const float* __re
             }
         }
     }
-    if (STAGE_GEMM_TN_F16) {                              // back to true units: 2^-(dY column scale + X column scale)
+    // back to true units: 2^-(dY column scale + X column scale)
 #pragma unroll
-        for (int i = 0; i < 2; i++)
+    for (int i = 0; i < 2; i++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int ua = __builtin_amdgcn_ds_bpermute(4 * h_row_of(r, h), upA[i]);
+        for (int r = 0; r < 16; r++) {
+            const int ua = __builtin_amdgcn_ds_bpermute(4 * h_row_of(r, h), upA[i]);
 #pragma unroll
-                for (int j = 0; j < 2; j++) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], 254 - ua - upB[j]);
-            }
-    }
+            for (int j = 0; j < 2; j++) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], 254 - ua - upB[j]);
+        }
     // C/D layout of the 32x32 MFMA: col = lane & 31 (k), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (n)
     float* po = part + (size_t)split * N * K;
 #pragma unroll
@@ -1196,7 +885,7 @@ __global__ __launch_bounds__(64 * TW_WAVES, 2) void gemm_tn_wide_kernel(const fl
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
     float bsum = 0.f;
-    int ebu[2] = {0, 0};                                  // fp16 mode: running exponents of the two unit columns this lane prepares
+    int ebu[2] = {0, 0};                                  // running exponents of the two unit columns this lane prepares
     int upA[2] = {254, 254}, upB[3] = {254, 254, 254};    // and the scale fields in force for the tiles this wave consumes
     float va[2][2][8], ga[GATE != 0 ? 2 : 1][8];          // [buffer][unit][row]
     bool abl_fw[2] = {false, false};
@@ -1238,72 +927,46 @@ __global__ __launch_bounds__(64 * TW_WAVES, 2) void gemm_tn_wide_kernel(const fl
 #pragma unroll
                 for (int r = 0; r < 8; r++) bsum += v[r];
             }
-            if (STAGE_GEMM_TN_F16) {   // planes 0 / 1 = hi / lo, the slot of plane 2 carries the exponent change of the column
-                const int du = h_track8(v, ebu[u]);
-                uint4 vh, vl;
-                h_split8(v, ebu[u], vh, vl);
-                exb[(u_mine[u] * 3 + 0) * 64 + lane] = vh;
-                exb[(u_mine[u] * 3 + 1) * 64 + lane] = vl;
-                reinterpret_cast<int*>(&exb[(u_mine[u] * 3 + 2) * 64])[lane] = du;
-                continue;
-            }
-            unsigned p[4][3];
-#pragma unroll
-            for (int i = 0; i < 4; i++) s_split3(v[2 * i], v[2 * i + 1], p[i]);
-#pragma unroll
-            for (int s = 0; s < STAGE_GEMM_TERMS; s++) exb[(u_mine[u] * 3 + s) * 64 + lane] = make_uint4(p[0][s], p[1][s], p[2][s], p[3][s]);
+            // planes 0 / 1 = hi / lo, the slot of plane 2 carries the exponent change of the column
+            const int du = h_track8(v, ebu[u]);
+            uint4 vh, vl;
+            h_split8(v, ebu[u], vh, vl);
+            exb[(u_mine[u] * 3 + 0) * 64 + lane] = vh;
+            exb[(u_mine[u] * 3 + 1) * 64 + lane] = vl;
+            reinterpret_cast<int*>(&exb[(u_mine[u] * 3 + 2) * 64])[lane] = du;
         }
         __syncthreads();
-        if (STAGE_GEMM_TN_F16) {
-            sf16x8 a[2][2];
-            int dA[2], dB[3];
+        sf16x8 a[2][2];
+        int dA[2], dB[3];
 #pragma unroll
-            for (int t = 0; t < 2; t++) {
+        for (int t = 0; t < 2; t++) {
 #pragma unroll
-                for (int s2 = 0; s2 < 2; s2++) a[t][s2] = __builtin_bit_cast(sf16x8, exb[((pn * 2 + t) * 3 + s2) * 64 + lane]);
-                dA[t] = reinterpret_cast<const int*>(&exb[((pn * 2 + t) * 3 + 2) * 64])[lane];
-            }
-#pragma unroll
-            for (int j = 0; j < 3; j++) dB[j] = reinterpret_cast<const int*>(&exb[((TW_NA + pk * 3 + j) * 3 + 2) * 64])[lane];
-            if (__any((dA[0] | dA[1] | dB[0] | dB[1] | dB[2]) != 0)) {   // a column's scale moved: bring the accumulators along
-#pragma unroll
-                for (int i = 0; i < 2; i++) {
-#pragma unroll
-                    for (int r = 0; r < 16; r++) {
-                        const int dr = __builtin_amdgcn_ds_bpermute(4 * h_row_of(r, h), dA[i]);
-#pragma unroll
-                        for (int j = 0; j < 3; j++) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], dr + dB[j]);
-                    }
-                    upA[i] += dA[i];
-                }
-#pragma unroll
-                for (int j = 0; j < 3; j++) upB[j] += dB[j];
-            }
-#pragma unroll
-            for (int j = 0; j < 3; j++) {
-                sf16x8 b[2];
-#pragma unroll
-                for (int s2 = 0; s2 < 2; s2++) b[s2] = __builtin_bit_cast(sf16x8, exb[((TW_NA + pk * 3 + j) * 3 + s2) * 64 + lane]);
-#pragma unroll
-                for (int i = 0; i < 2; i++) acc[i][j] = h_mfma_terms(a[i], b, acc[i][j]);
-            }
-            return;
+            for (int s2 = 0; s2 < 2; s2++) a[t][s2] = __builtin_bit_cast(sf16x8, exb[((pn * 2 + t) * 3 + s2) * 64 + lane]);
+            dA[t] = reinterpret_cast<const int*>(&exb[((pn * 2 + t) * 3 + 2) * 64])[lane];
         }
-        sbf16x8 a[2][3];
 #pragma unroll
-        for (int t = 0; t < 2; t++)
-#pragma unroll
-            for (int s = 0; s < STAGE_GEMM_TERMS; s++) a[t][s] = __builtin_bit_cast(sbf16x8, exb[((pn * 2 + t) * 3 + s) * 64 + lane]);
-#pragma unroll
-        for (int j = 0; j < 3; j++) {
-            sbf16x8 b[3];
-#pragma unroll
-            for (int s = 0; s < STAGE_GEMM_TERMS; s++) b[s] = __builtin_bit_cast(sbf16x8, exb[((TW_NA + pk * 3 + j) * 3 + s) * 64 + lane]);
+        for (int j = 0; j < 3; j++) dB[j] = reinterpret_cast<const int*>(&exb[((TW_NA + pk * 3 + j) * 3 + 2) * 64])[lane];
+        if (__any((dA[0] | dA[1] | dB[0] | dB[1] | dB[2]) != 0)) {   // a column's scale moved: bring the accumulators along
 #pragma unroll
             for (int i = 0; i < 2; i++) {
-                // kept cross terms, smallest first
-                acc[i][j] = s_mfma_terms(a[i], b, acc[i][j]);
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int dr = __builtin_amdgcn_ds_bpermute(4 * h_row_of(r, h), dA[i]);
+#pragma unroll
+                    for (int j = 0; j < 3; j++) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], dr + dB[j]);
+                }
+                upA[i] += dA[i];
             }
+#pragma unroll
+            for (int j = 0; j < 3; j++) upB[j] += dB[j];
+        }
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+            sf16x8 b[2];
+#pragma unroll
+            for (int s2 = 0; s2 < 2; s2++) b[s2] = __builtin_bit_cast(sf16x8, exb[((TW_NA + pk * 3 + j) * 3 + s2) * 64 + lane]);
+#pragma unroll
+            for (int i = 0; i < 2; i++) acc[i][j] = h_mfma_terms(a[i], b, acc[i][j]);
         }
     };
     if (mbeg < mend) {   // workgroup-uniform bounds: the barriers match
@@ -1318,16 +981,15 @@ __global__ __launch_bounds__(64 * TW_WAVES, 2) void gemm_tn_wide_kernel(const fl
         }
     }
     // C/D layout of the 32x32 MFMA: col = lane & 31 (k), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (n)
-    if (STAGE_GEMM_TN_F16) {                              // back to true units: 2^-(dY column scale + X column scale)
+    // back to true units: 2^-(dY column scale + X column scale)
 #pragma unroll
-        for (int i = 0; i < 2; i++)
+    for (int i = 0; i < 2; i++)
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int ua = __builtin_amdgcn_ds_bpermute(4 * h_row_of(r, h), upA[i]);
+        for (int r = 0; r < 16; r++) {
+            const int ua = __builtin_amdgcn_ds_bpermute(4 * h_row_of(r, h), upA[i]);
 #pragma unroll
-                for (int j = 0; j < 3; j++) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], 254 - ua - upB[j]);
-            }
-    }
+            for (int j = 0; j < 3; j++) acc[i][j][r] = __builtin_ldexpf(acc[i][j][r], 254 - ua - upB[j]);
+        }
     float* po = part + (size_t)split * N * K;
 #pragma unroll
     for (int i = 0; i < 2; i++)
@@ -1555,16 +1217,13 @@ int stage_gemm_tn_stream(const float* dY, const void* gate, int gate_kind, const
                          long long M, int N, int K, int* S_io, long* rows_per_split_io, void* stream) {
     // buffer addressing: every operand must be smaller than 2 GiB
     // rows: from 4096; from 1024 for K <= 128 (M = 3200: 27 -> 21 us; wider K loses to the tiled fp32 kernel there)
-    static const long long min_m_env = getenv("STAGE_GEMM_STREAM_MIN_M") ? atoll(getenv("STAGE_GEMM_STREAM_MIN_M")) : 0;
-    const long long min_m_tn = min_m_env ? min_m_env : (K <= 128 ? 1024 : 4096);
+    const long long min_m_tn = K <= 128 ? 1024 : 4096;
     if (M < min_m_tn || M * (long long)N * 4 >= (1ll << 31) || M * (long long)K * 4 >= (1ll << 31)) return 1;
     if (!gate) gate_kind = 0;
     const float* G = (const float*)gate;
     int S = *S_io;
     long rows_per_split = *rows_per_split_io;
-    static const bool no_wide = getenv("STAGE_GEMM_TN_NOWIDE") != nullptr;
-    static const bool no_share_w = getenv("STAGE_GEMM_TN_NOSHARE") != nullptr;
-    if (K > 128 && !no_wide && !no_share_w) {
+    if (K > 128) {
         // 128 x 384 tiles, one 8-wave workgroup per CU: as many slabs as give whole rounds of 256 workgroups (never more
         // than the workspace was sized for)
         const int wps = ((N + 127) / 128) * ((K + 383) / 384);
@@ -1580,8 +1239,7 @@ int stage_gemm_tn_stream(const float* dY, const void* gate, int gate_kind, const
         *S_io = S;
         *rows_per_split_io = rps;
         dim3 gridw((N + 127) / 128, (K + 383) / 384, S);
-        static const bool no_quad = getenv("STAGE_GEMM_TN_NOQUAD") != nullptr;
-        if (STAGE_GEMM_TN_F16 && !no_quad && gate_kind != 1 && N % 4 == 0 && K % 4 == 0 && (((uintptr_t)dY | (uintptr_t)X) & 15) == 0 &&
+        if (gate_kind != 1 && N % 4 == 0 && K % 4 == 0 && (((uintptr_t)dY | (uintptr_t)X) & 15) == 0 &&
             (gate_kind != 2 || (((uintptr_t)gate & 15) == 0 && rows_per_split % 16 == 0))) {
             const int ldsq = 2 * 2 * 16 * 2 * 64 * (int)sizeof(uint4) + 2 * 16 * 32 * (int)sizeof(int);
 #define LAUNCH_TNQ(GT)                                                                                                 \
@@ -1620,8 +1278,7 @@ int stage_gemm_tn_stream(const float* dY, const void* gate, int gate_kind, const
     }
     dim3 grid((N + 127) / 128, (K + 127) / 128, S);
     {   // K <= 128: the quad kernel with ONE X quad (row-wise 16-byte loads; same conditions as above)
-        static const bool no_quad1 = getenv("STAGE_GEMM_TN_NOQUAD") != nullptr;
-        if (STAGE_GEMM_TN_F16 && !no_quad1 && gate_kind != 1 && N % 4 == 0 && K % 4 == 0 && (((uintptr_t)dY | (uintptr_t)X) & 15) == 0 &&
+        if (gate_kind != 1 && N % 4 == 0 && K % 4 == 0 && (((uintptr_t)dY | (uintptr_t)X) & 15) == 0 &&
             (gate_kind != 2 || (((uintptr_t)gate & 15) == 0 && rows_per_split % 16 == 0))) {
             const int ldsq1 = 2 * 2 * 8 * 2 * 64 * (int)sizeof(uint4) + 2 * 8 * 32 * (int)sizeof(int);
 #define LAUNCH_TNQ1(GT)                                                                                                \
@@ -1641,16 +1298,9 @@ int stage_gemm_tn_stream(const float* dY, const void* gate, int gate_kind, const
             return 0;
         }
     }
-    static const bool no_share = getenv("STAGE_GEMM_TN_NOSHARE") != nullptr;
 #define LAUNCH_TNS(GT)                                                                                                 \
-    do {                                                                                                               \
-        if (no_share)                                                                                                  \
-            hipLaunchKernelGGL(gemm_tn_stream_kernel<GT>, grid, dim3(256), 0, (hipStream_t)stream, dY, G, X, part,      \
-                               part_b, (long)M, N, K, rows_per_split);                                                 \
-        else                                                                                                           \
-            hipLaunchKernelGGL(gemm_tn_share_kernel<GT>, grid, dim3(256), 0, (hipStream_t)stream, dY, G, X, part,       \
-                               part_b, (long)M, N, K, rows_per_split);                                                 \
-    } while (0)
+    hipLaunchKernelGGL(gemm_tn_share_kernel<GT>, grid, dim3(256), 0, (hipStream_t)stream, dY, G, X, part, part_b,      \
+                       (long)M, N, K, rows_per_split)
     if (gate_kind == 2) LAUNCH_TNS(2);
     else if (gate_kind == 1) LAUNCH_TNS(1);
     else LAUNCH_TNS(0);

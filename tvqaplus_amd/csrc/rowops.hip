@@ -7,7 +7,6 @@
 //   * masked max over a (ranged) sequence axis forward / backward          model/stage.py:503-505, 425-432, 532-533
 //   * deterministic two-stage column reductions for the affine/bias gradients
 // One "row group" of LPR lanes (power of two, 4..64) owns one row; a wave processes 64/LPR rows at a time.
-#include <stdlib.h>
 #include "common.h"
 #include "../../include/stage_hip.h"
 
@@ -597,7 +596,7 @@ static int ln_fwd_launch(RowSrcT<T> src, const float* gamma, const float* beta, 
     const int rows_per_block = 4 * (64 / LPR);
     const int q4 = (MODE == 0) ? K / 4 : src.D / 4;
     const int nq = (MODE == 0) ? (q4 + LPR - 1) / LPR : (q4 == LPR ? 1 : 0);   // quads per lane; MODE 1 needs D/4 == LPR
-    if (nq >= 1 && nq <= 4 && rows < (1ll << 31) && !getenv("STAGE_LN_GENERIC")) {   // fixed column quads per lane
+    if (nq >= 1 && nq <= 4 && rows < (1ll << 31)) {   // fixed column quads per lane
         const int gridf = stage_grid_for(rows, rows_per_block * LN_UR, GRID_CAP * 2);
         const bool dr = p_drop > 0.f;
         const uint64_t sd = dr ? (uint64_t)seed : 0;
@@ -650,7 +649,7 @@ static int ln_bwd_launch(RowSrcT<T> src, const T* dy, const float* mean, const f
     float* part = (float*)ws;
     const int q4 = (MODE == 0) ? K / 4 : src.D / 4;
     const int nq = (MODE == 0) ? (q4 + LPR - 1) / LPR : (q4 == LPR ? 1 : 0);
-    const bool fast = nq >= 1 && nq <= 4 && rows < (1ll << 31) && !getenv("STAGE_LN_GENERIC");
+    const bool fast = nq >= 1 && nq <= 4 && rows < (1ll << 31);
     if (fast) {
         const bool dr = p_drop > 0.f;
         const uint64_t sd = dr ? (uint64_t)seed : 0;

@@ -1144,8 +1144,7 @@ static int fus_num_wgs(int N, int Li = 1 << 20) {
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
         cus = v;
     }
-    static const int env_wgs = getenv("STAGE_K1_BWD_WGS") ? atoi(getenv("STAGE_K1_BWD_WGS")) : 0;   // developer switch
-    int G = env_wgs > 0 ? env_wgs : cus;      // one workgroup per CU (256 registers, up to 157 KB of LDS)
+    int G = cus;      // one workgroup per CU (256 registers, up to 157 KB of LDS)
     if (G > FUS_MAX_WGS) G = FUS_MAX_WGS;
     const long few = ((long)N * Li + 3) / 4;          // small problems: at least ~4 frames per workgroup (per-workgroup slab + set-up)
     if (G > few) G = (int)few;
@@ -1173,9 +1172,8 @@ static int fus_launch(const TD* dA, const float* ext, const float* Cn, const TD*
     const size_t base = ((size_t)Lr * (FUS_P1_F16 ? FQLD : FLDQ) + FusLay<RT>::QT_FLOATS + (size_t)CR * FusLay<RT>::LG) * sizeof(float) + 32;
     const size_t with_da = base + (size_t)CR * FD * sizeof(float);
     // dA of a frame stays in LDS between the phases when it fits (the video shape) and the uniform phase 2 applies
-    static const bool no_ldsa = getenv("STAGE_K1_BWD_NOLDSA") != nullptr;   // developer switch
     const bool unif = (Lqa & 3) == 0 && ((CR >> 2) % 10) == 0;
-    const bool ldsa = !no_ldsa && unif && NW == 8 && OCC == 2 && with_da <= 160 * 1024;
+    const bool ldsa = unif && NW == 8 && OCC == 2 && with_da <= 160 * 1024;
     const size_t lds = ldsa ? with_da : base;
     const dim3 grid(G), block(64 * NW);
     unsigned long long* tim = (unsigned long long*)(getenv("STAGE_K1_BWD_TIM") ? strtoull(getenv("STAGE_K1_BWD_TIM"), 0, 0) : 0ull);

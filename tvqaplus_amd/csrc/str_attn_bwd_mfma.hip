@@ -211,7 +211,7 @@ int stage_str_attn_bwd_dq_mfma(const float* dA, const float* Sn, const float* dS
     if (blocks > 768) blocks = 768;   // ~3 workgroups of 4 waves per CU, waves stride the items
     const dim3 grid((unsigned)blocks), block(256);
     const int rt = (Lr + 15) / 16;
-    const bool t4 = Lr - 16 * (rt - 1) <= 4 && !getenv("STAGE_K1_DQ_NO_T4");
+    const bool t4 = Lr - 16 * (rt - 1) <= 4;
 #define LAUNCH_DQ(R, T) hipLaunchKernelGGL((str_attn_bwd_dq_mfma_kernel<R, T>), grid, block, 0, st, dA, Sn, dS, Cn, dQraw, dQn, N, NA, Li, Lqa, Lr, D)
     switch (rt) {
         case 1: if (t4) LAUNCH_DQ(1, true); else LAUNCH_DQ(1, false); break;

@@ -633,16 +633,14 @@ static int launch_d128_t(const float* Cn, const TQ* Q, const float* cm, const fl
     const int CR = NA * Lqa, CT = (CR + 15) / 16;
     // slices of the context tiles: enough work items (frames x slices) to balance ~2048 waves, >= 3 tiles per item
     int slices = 1;
-    if (getenv("STAGE_K1_SLICES")) slices = atoi(getenv("STAGE_K1_SLICES"));
-    else while (slices < 4 && (long)N * Li * slices < 8192 && CT / (slices + 1) >= 3) slices++;
+    while (slices < 4 && (long)N * Li * slices < 8192 && CT / (slices + 1) >= 3) slices++;
     const int tps = (CT + slices - 1) / slices;
     slices = (CT + tps - 1) / tps;
     uint32_t th = TRAIN ? drop_thresh16(p_drop) : 0u;
     if (TRAIN && th == 0u) th = 1u;
     const float ik = TRAIN ? 1.0f / (1.0f - p_drop) : 1.0f;
     unsigned long long* tim = (unsigned long long*)(getenv("STAGE_K1_TIM") ? strtoull(getenv("STAGE_K1_TIM"), 0, 0) : 0ull);
-    static const bool no_wgf = getenv("STAGE_K1_NO_WGF") != nullptr;
-    if constexpr (RT >= 3) if (!no_wgf) {
+    if constexpr (RT >= 3) {
         // one frame copy per 4-wave workgroup (kernel comment); two workgroups per CU by registers
         constexpr bool f16l = K1_F16;
         // K1_F16: prepared fp16 pairs + transposed fp16 planes; otherwise raw + prepared fp32 copy
@@ -664,36 +662,34 @@ static int launch_d128_t(const float* Cn, const TQ* Q, const float* cm, const fl
                            CT, (uint64_t)seed, th, ik, tk.word, tk.base, tim, fmap, (const int2*)cq);
         STAGE_LAUNCH_CHECK_TICKET(tk);
         return 0;
+    } else {     // Lr <= 32 that the register kernel declined: per-wave frame copies
+        if (cq) return STAGE_ERR_SHAPE;      // compact region rows: the workgroup-staged fp16 kernel above (and the register kernel) only
+        const size_t wave_bytes = ((size_t)(Lr + 1) * LDQ + 2 * RT * 16 + (size_t)tps * 16) * sizeof(float);
+        // waves per workgroup: the grouping that lets the most waves share a CU's 160 KB of LDS (Lr = 50: 27.9 KB per wave,
+        // 5 one-wave workgroups fit where 2 two-wave ones would); ties go to the larger workgroup
+        int wpb = 1, best = 0;
+        for (int cand = 4; cand >= 1; cand >>= 1) {
+            const size_t per_wg = (cand * wave_bytes + 511) / 512 * 512;          // allocation granularity
+            int waves = (int)((160 * 1024) / per_wg) * cand;
+            if (waves > 8) waves = 8;
+            if (waves > best) { best = waves; wpb = cand; }
+        }
+        const size_t lds = wpb * wave_bytes;
+        auto kern = str_attn_fwd_d128_kernel<RT, KL, PERM, TRAIN, VEC_S, false, TQ, false>;
+        if constexpr (std::is_same<TQ, float>::value) { if (fmap) kern = str_attn_fwd_d128_kernel<RT, KL, PERM, TRAIN, VEC_S, false, TQ, true>; }
+        else if (fmap) return STAGE_ERR_SHAPE;
+        if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const long items = (long)N * Li * slices;
+        const int waves_per_cu = best > 0 ? best : 1;
+        long blocks = (256L * waves_per_cu + wpb - 1) / wpb;         // one resident round of waves; they stride the items
+        if (blocks * wpb > items) blocks = (items + wpb - 1) / wpb;
+        const StageTicket tk = stage_next_ticket((unsigned int)items);   // every processed item draws one ticket (common.h)
+        if (!tk.word) return (int)hipErrorOutOfMemory;
+        hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * wpb), lds, st, Cn, Q, cm, qm, A, S, Sn, N, NA, Li, Lqa, Lr,
+                           scale, slices, tps, (uint64_t)seed, th, ik, tk.word, tk.base, tim, fmap, (const int2*)nullptr);
+        STAGE_LAUNCH_CHECK_TICKET(tk);
+        return 0;
     }
-    if (cq) return STAGE_ERR_SHAPE;      // compact region rows: the workgroup-staged fp16 kernel above (and the register kernel) only
-    const size_t wave_bytes = ((size_t)(Lr + 1) * LDQ + 2 * RT * 16 + (size_t)tps * 16) * sizeof(float);
-    // waves per workgroup: the grouping that lets the most waves share a CU's 160 KB of LDS (Lr = 50: 27.9 KB per wave,
-    // 5 one-wave workgroups fit where 2 two-wave ones would); ties go to the larger workgroup
-    int wpb = 1, best = 0;
-    for (int cand = 4; cand >= 1; cand >>= 1) {
-        const size_t per_wg = (cand * wave_bytes + 511) / 512 * 512;          // allocation granularity
-        int waves = (int)((160 * 1024) / per_wg) * cand;
-        if (waves > 8) waves = 8;
-        if (waves > best) { best = waves; wpb = cand; }
-    }
-    if (getenv("STAGE_K1_WPB")) wpb = atoi(getenv("STAGE_K1_WPB"));
-    const size_t lds = wpb * wave_bytes;
-    auto kern = str_attn_fwd_d128_kernel<RT, KL, PERM, TRAIN, VEC_S, false, TQ, false>;
-    if constexpr (std::is_same<TQ, float>::value) { if (fmap) kern = str_attn_fwd_d128_kernel<RT, KL, PERM, TRAIN, VEC_S, false, TQ, true>; }
-    else if (fmap) return STAGE_ERR_SHAPE;
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const long items = (long)N * Li * slices;
-    int waves_per_cu = best > 0 ? best : 1;
-    if (getenv("STAGE_K1_WPC")) waves_per_cu = atoi(getenv("STAGE_K1_WPC"));
-    if (waves_per_cu < 1) waves_per_cu = 1;
-    long blocks = (256L * waves_per_cu + wpb - 1) / wpb;         // one resident round of waves; they stride the items
-    if (blocks * wpb > items) blocks = (items + wpb - 1) / wpb;
-    const StageTicket tk = stage_next_ticket((unsigned int)items);   // every processed item draws one ticket (common.h)
-    if (!tk.word) return (int)hipErrorOutOfMemory;
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * wpb), lds, st, Cn, Q, cm, qm, A, S, Sn, N, NA, Li, Lqa, Lr,
-                       scale, slices, tps, (uint64_t)seed, th, ik, tk.word, tk.base, tim, fmap, (const int2*)nullptr);
-    STAGE_LAUNCH_CHECK_TICKET(tk);
-    return 0;
 }
 
 template <int RT, bool TRAIN, typename TQ>
@@ -703,8 +699,7 @@ static int launch_d128(const float* Cn, const TQ* Q, const float* cm, const floa
     const int rem = Lr - 16 * (RT - 1);
     // 16-byte score stores need rows that start on 8 bytes only (the hardware takes dwordx4 at dword alignment; 8-byte rows measured
     // as fast as 16-byte ones); odd Lr keeps the scalar stores
-    static const bool no_vec8 = getenv("STAGE_K1_NO_VEC8") != nullptr;
-    const bool vec = (Lr & 3) == 0 || ((Lr & 1) == 0 && !no_vec8);
+    const bool vec = (Lr & 1) == 0;
 #define ARGS Cn, Q, cm, qm, A, S, Sn, N, NA, Li, Lqa, Lr, scale, p_drop, seed, st, fmap, cq
     if (rem == 16) return vec ? launch_d128_t<RT, 4, false, TRAIN, true, TQ>(ARGS) : launch_d128_t<RT, 4, false, TRAIN, false, TQ>(ARGS);
     switch ((rem + 3) / 4) {
@@ -772,11 +767,10 @@ static int str_attn_fwd_dispatch(const float* Cn, const float* Q, const float* c
         return stage_str_attn_fwd_v1(Cn, Q, c_mask, q_mask, A, S_raw, S_norm, N, NA, Li, Lqa, Lr, D, scale, p_drop, seed,
                                      stream);
     }
-    if (!getenv("STAGE_K1_LDS")) {   // register-resident kernel for Lr <= 32 (str_attn_fwd_reg.hip); 1 = not handled
-        const int rc = stage_str_attn_fwd_reg(Cn, Q, c_mask, q_mask, A, S_raw, S_norm, N, NA, Li, Lqa, Lr, D, scale, p_drop,
-                                              seed, stream, fmap, cq);
-        if (rc != 1) return rc;
-    }
+    // register-resident kernel for Lr <= 32 (str_attn_fwd_reg.hip); 1 = not handled
+    const int rc = stage_str_attn_fwd_reg(Cn, Q, c_mask, q_mask, A, S_raw, S_norm, N, NA, Li, Lqa, Lr, D, scale, p_drop, seed,
+                                          stream, fmap, cq);
+    if (rc != 1) return rc;
     return str_attn_fwd_d128_t<float>(Cn, Q, c_mask, q_mask, A, S_raw, S_norm, N, NA, Li, Lqa, Lr, scale, p_drop, seed, stream, fmap, cq);
 }
 
@@ -806,11 +800,9 @@ extern "C" int stage_str_attn_fwd_bf16(const float* Cn, const void* Q, const flo
                                        float p_drop, unsigned long long seed, void* stream) {
     if (N <= 0 || Li <= 0) return 0;
     if (D != DD || Lr < 1 || Lr > 64 || Lqa < 1 || NA < 1) return STAGE_ERR_SHAPE;
-    if (!getenv("STAGE_K1_LDS")) {
-        const int rc = stage_str_attn_fwd_reg_bf16(Cn, Q, c_mask, q_mask, A, S_raw, S_norm, N, NA, Li, Lqa, Lr, D, scale, p_drop,
-                                                   seed, stream);
-        if (rc != 1) return rc;
-    }
+    const int rc = stage_str_attn_fwd_reg_bf16(Cn, Q, c_mask, q_mask, A, S_raw, S_norm, N, NA, Li, Lqa, Lr, D, scale, p_drop, seed,
+                                               stream);
+    if (rc != 1) return rc;
     return str_attn_fwd_d128_t<stage_bf16>(Cn, (const stage_bf16*)Q, c_mask, q_mask, (stage_bf16*)A, S_raw, S_norm, N, NA, Li, Lqa,
                                            Lr, scale, p_drop, seed, stream);
 }

@@ -17,7 +17,6 @@
 //               weights ARE the A operand of stage 2 (contraction index g <-> region Rk(g, k); both operands agree)
 //   stage 2  A tile (ctx x d) = S_ . Q -> lane owns 4 consecutive d of context rows 4g+reg: 16-B stores, 256 B per row.
 // Region permutation of the LAST region tile (PERM/KL) as in str_attn_fwd.hip: tile row 4g+k holds region base + g + 4k.
-#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 #include "../../include/stage_hip.h"
@@ -510,9 +509,7 @@ static int launch_reg_t(const float* Cn, const TQ* Q, const float* cm, const flo
     const int CR = NA * Lqa, CT = (CR + 15) / 16;
     // slices of the context tiles: enough work items (frames x slices) to balance ~2048 waves, >= 3 tiles per item
     int slices = 1;
-    if (getenv("STAGE_K1_SLICES")) slices = atoi(getenv("STAGE_K1_SLICES"));
-    else while (slices < 4 && (long)N * Li * slices < 8192 && CT / (slices + 1) >= 3) slices++;
-    if (slices < 1) slices = 1;
+    while (slices < 4 && (long)N * Li * slices < 8192 && CT / (slices + 1) >= 3) slices++;
     const int tps = (CT + slices - 1) / slices;
     slices = (CT + tps - 1) / tps;
     const long items = (long)N * Li * slices;
@@ -523,7 +520,6 @@ static int launch_reg_t(const float* Cn, const TQ* Q, const float* cm, const flo
     const float ik = TRAIN ? 1.0f / (1.0f - p_drop) : 1.0f;
     // ~70 % of the items by static stride, the tail by tickets (at least one dynamic round)
     int static_rounds = (int)((items * 7) / (blocks * 4 * 10));
-    if (getenv("STAGE_K1_STATIC")) static_rounds = atoi(getenv("STAGE_K1_STATIC"));
     if (static_rounds < 1) static_rounds = 1;
     const long n_waves = blocks * 4;
     while (static_rounds > 1 && (long)static_rounds * n_waves > items) static_rounds--;
@@ -556,8 +552,7 @@ static int launch_reg(const float* Cn, const TQ* Q, const float* cm, const float
                       int N, int NA, int Li, int Lqa, int Lr, float scale, float p_drop, unsigned long long seed,
                       hipStream_t st, const int* fmap, const int* cq) {
     const int rem = Lr - 16 * (RT - 1);
-    static const bool no_vec8 = getenv("STAGE_K1_NO_VEC8") != nullptr;       // (see str_attn_fwd.hip: 16-byte stores at 8-byte row starts)
-    const bool vec = (Lr & 3) == 0 || ((Lr & 1) == 0 && !no_vec8);
+    const bool vec = (Lr & 1) == 0;       // (see str_attn_fwd.hip: 16-byte stores at 8-byte row starts)
 #define ARGS Cn, Q, cm, qm, A, S, Sn, N, NA, Li, Lqa, Lr, scale, p_drop, seed, st, fmap, cq
     if (rem == 16) return vec ? launch_reg_t<RT, 4, false, TRAIN, true, TQ>(ARGS) : launch_reg_t<RT, 4, false, TRAIN, false, TQ>(ARGS);
     switch ((rem + 3) / 4) {

@@ -735,8 +735,7 @@ static int lng_bwd(const void* dA, const void* A, const float* ext, const void* 
     hipLaunchKernelGGL(lng_slab_sum_kernel, dim3((unsigned)((C + 255) / 256)), dim3(256), 0, st, (const float*)part, dCn, nchunks, C);
     STAGE_LAUNCH_CHECK();
     if constexpr (sizeof(T) == 2) {
-        static const bool dq16 = getenv("STAGE_LONG_DQ16") != nullptr;      // developer switch: the 16-region fp32-MFMA kernel
-        if (D == 256 && !dq16) {
+        if (D == 256) {
             const long items32 = (long)N * Li * ((Lr + 31) / 32) * 2;
             hipLaunchKernelGGL(str_attn_long_bwd_dq32_kernel, dim3((unsigned)((items32 + 3) / 4)), dim3(256), 0, st, (const __hip_bfloat16*)dA, Sn,
                                (const float*)dS, (const __hip_bfloat16*)Cn, dQraw, dQn, N, NA, Li, Lqa, Lr, (const int*)fnv);
@@ -744,7 +743,7 @@ static int lng_bwd(const void* dA, const void* A, const float* ext, const void* 
             return 0;
         }
     }
-    const bool dq_split = D > 128 && !(sizeof(T) == 2 && !getenv("STAGE_LONG_DQ_SPLIT"));
+    const bool dq_split = D > 128;      // fp32 storage only: D = 256 in bf16 went to the 32-region kernel above
     const long items2 = (long)N * Li * ((Lr + 15) / 16) * (dq_split ? D / 128 : 1);
 #define LNG_Q(DTV, DTWV)                                                                                                   \
     hipLaunchKernelGGL((str_attn_long_bwd_dq_kernel<T, DTV, DTWV>), dim3((unsigned)((items2 + 3) / 4)), dim3(256), 0, st, (const T*)dA, Sn, \
@@ -755,7 +754,7 @@ static int lng_bwd(const void* dA, const void* A, const float* ext, const void* 
         case 64: LNG_Q(4, 4); break;
         case 128: LNG_Q(8, 8); break;
         default:
-            if (sizeof(T) == 2 && !getenv("STAGE_LONG_DQ_SPLIT")) LNG_Q(16, 16); else LNG_Q(16, 8);
+            if constexpr (sizeof(T) == 4) LNG_Q(16, 8);
             break;
     }
 #undef LNG_Q

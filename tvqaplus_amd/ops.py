@@ -605,7 +605,7 @@ def l2norm(x: torch.Tensor, p: float = 0.0, seed: int = 0) -> torch.Tensor:
 # ---------------------------------------------------------------------------------------------------------------
 import os as _os
 
-_K1_BWD_UNFUSED = _os.environ.get("STAGE_K1_BWD_UNFUSED") is not None   # developer switch (cross-check in the tests)
+_K1_BWD_UNFUSED = False   # True: the backward as separate kernels (the tests set it for their cross-check)
 
 
 def _fold_dsn(dS, dSn, Sn, scale):
@@ -915,7 +915,7 @@ class _MHACoreQKV(torch.autograd.Function):
 
 
 def mha_core_qkv_supported(L: int, D: int, nh: int) -> bool:
-    return _os.environ.get("STAGE_MHA_SCALAR") is None and _os.environ.get("STAGE_NO_FUSED_QKV") is None and \
+    return _os.environ.get("STAGE_MHA_SCALAR") is None and \
         bool(_lib.load().stage_mha_core_recomputes(L, D, nh)) and D % 8 == 0
 
 

@@ -259,9 +259,6 @@ class STAGE(nn.Module):
         self.temporal_criterion = nn.CrossEntropyLoss(reduction="sum")
         self.classifier = _LinearWrapperParams(self.hsz * 2 if self.add_local else self.hsz, 1, self.dropout,
                                                relu=False)
-        # developer switch: False (or STAGE_NO_FUSE_LN_DWCONV=1) = separate LayerNorm and depthwise-conv kernels
-        self.fuse_ln_dwconv = os.environ.get("STAGE_NO_FUSE_LN_DWCONV") is None
-        self.fuse_ln_max = os.environ.get("STAGE_NO_FUSE_LN_MAX") is None
         # opt-in: correct, but 0.6 ms SLOWER per step as built (DESIGN.md finding 25) -- the register budget forces the variant
         # without the weight-chunk prefetch
         self.fuse_input_ln = os.environ.get("STAGE_FUSE_INPUT_LN") is not None
@@ -270,8 +267,7 @@ class STAGE(nn.Module):
         # same dropout streams: tests/test_hip_groups.py holds the two equal.  Groups cover fp32 storage and encoder blocks
         # without self-attention; everything else falls back to the per-op path group by group.
         self.use_groups = os.environ.get("STAGE_NO_GROUPS") is None
-        self.gate_shared = os.environ.get("STAGE_NO_PARAM_GATE") is None   # groups.gate for the modules applied to several streams
-        self._gate_map = {}
+        self._gate_map = {}     # groups.gate for the modules applied to several streams (_open_gates)
         # ragged token rows (tvqaplus_amd/ragged.py): the (N, 5, Li, Lqa, .) kernels run on the rows that can reach an output or a
         # gradient -- live frames x (valid words + the classifier encoder's convolution halo).  False / STAGE_NO_RAGGED=1: every padded
         # row is computed, as the reference does.  Needs the K-group path at hsz = 128 (otherwise the dense path runs, silently: it is
@@ -364,8 +360,7 @@ class STAGE(nn.Module):
         ``pool_mask`` (M, L): the caller only needs the masked max of the block's output over L (the classifier head,
         model/stage.py:503) -- the final LayerNorm and the max run as one pass and (M, D) is returned."""
         M, L, D = x.shape
-        if (self._grouped() and blk.num_heads == 0 and blk.n_conv >= 1 and x.dtype == torch.float32 and self.fuse_ln_dwconv
-                and self.fuse_ln_max):
+        if self._grouped() and blk.num_heads == 0 and blk.n_conv >= 1 and x.dtype == torch.float32:
             k = blk.conv[0].depthwise_conv.weight.shape[-1]
             params = [self._g(w) for w in _block_params(blk)]
             y = self._try_group(lambda seeds: groups.encoder_block(x, blk.position_encoding.rows(L), pool_mask, k, self._p(), seeds,
@@ -376,7 +371,7 @@ class STAGE(nn.Module):
         for i in range(blk.n_conv):
             c = blk.conv[i]
             ln, drop = blk.layer_norm[i], (i % 2 == 0)
-            if self.fuse_ln_dwconv and ops.ln_dwconv_supported(D, c.depthwise_conv.weight.shape[-1], pending.dtype):
+            if ops.ln_dwconv_supported(D, c.depthwise_conv.weight.shape[-1], pending.dtype):
                 # LayerNorm output only feeds the depthwise conv: one fused pass, never materialised
                 h, cur = ops.ln_dwconv(pending, self._g(ln.weight), self._g(ln.bias), self._g(c.depthwise_conv.weight),
                                        self._g(c.depthwise_conv.bias),
@@ -415,7 +410,7 @@ class STAGE(nn.Module):
                 a = ops.mha_core(q, k, v, mask, mha.nh, p=p_attn, seed=self._seed() if p_attn > 0 else 0)
             pending = ops.linear(a, self._g(mha.linears[3].weight), self._g(mha.linears[3].bias))
         if pool_mask is not None:
-            if self.fuse_ln_max and period == 0 and ops.ln_masked_max_supported(pending, L, D):
+            if period == 0 and ops.ln_masked_max_supported(pending, L, D):
                 return ops.ln_masked_max(pending, cur, blk.final_layer_norm.weight, blk.final_layer_norm.bias, pool_mask)
             y, _ = self._ln(pending, blk.final_layer_norm, res=cur, res_period=period)
             return ops.masked_max(y, pool_mask)
@@ -769,8 +764,7 @@ class STAGE(nn.Module):
         the ragged kernels do not cover (decided BEFORE anything is launched: hsz = 128 on the K-group path, one classifier-encoder
         block without self-attention, <= 40 QA words, even region / word counts <= 64), or no live row at all."""
         none = (None, {})
-        if not (self.use_ragged and self._grouped() and self.fuse_ln_dwconv and self.fuse_ln_max and a_embed.is_cuda
-                and a_embed.dtype == torch.float32):
+        if not (self.use_ragged and self._grouped() and a_embed.is_cuda and a_embed.dtype == torch.float32):
             return none
         N, NA, Lqa, D = a_embed.shape
         blocks = list(self.cls_encoder.stacked_encoderBlocks)
@@ -869,7 +863,7 @@ class STAGE(nn.Module):
         self._gate_map = {}
         # (both paths: the K-groups deliver into the sinks, and so do the per-kernel LayerNorm / Linear / LayerNorm->dwconv ops --
         # the bf16 storage mode runs the shared encoder once per stream and length bucket)
-        if not (self.gate_shared and self.training and torch.is_grad_enabled()):
+        if not (self.training and torch.is_grad_enabled()):
             return
         mods = [self.bert_word_encoding_fc, self.input_embedding, self.input_encoder]
         if self.flag_cnt == 2:
