@@ -508,6 +508,42 @@ int stage_grp_input_mlp_rag_fwd(const float* x, const int* src_rows, const float
 int stage_grp_input_mlp_rag_bwd(const float* dout, const float* x, const int* src_rows, const float* const* P, float* const* G,
                                 const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M,
                                 int K0, int H, int D, int l2, float p, const unsigned long long* seeds, void* stream);
+/* HALF-PRECISION FEATURE ROWS in the fp32 model (csrc/feat16.hip).  A loader may store the BERT / region features as fp16 or bf16
+ * (half the host -> device bytes); these entry points read such rows in place and convert them in registers -- exactly -- so that no
+ * fp32 image of the features (and, with l2, no normalised image) is ever written.  dtype: STAGE_DT_F16 / STAGE_DT_BF16.
+ * First stage of the input MLP: [l2 != 0: F.normalize, model/stage.py:256] -> LayerNorm(K0) + inverted dropout (model/stage.py:85-91,
+ * 98-104), row r reading x[src_rows ? src_rows[r] : r]; y0 (rows, K0) fp32, mean0 / rstd0 (rows).  The function, the dropout stream
+ * (indexed by r) and the order of the floating-point sums are those of stage_l2norm[_gather]_fwd + stage_layernorm[_gather]_fwd on the
+ * upcast rows.  The backward gives d gamma / d beta only (features are data), through a deterministic two-stage column reduction.
+ * Requirements: K0 % 4 == 0, 4 <= K0 <= 1024 (stage_feat16_supported), x 8-byte aligned with contiguous rows, rows < 2^31; anything
+ * else returns STAGE_ERR_SHAPE before a launch. */
+#define STAGE_DT_F16 1
+#define STAGE_DT_BF16 2
+int stage_feat16_supported(int K0, int dtype);
+int stage_feat16_ln_fwd(const void* x, int dtype, const int* src_rows, const float* gamma, const float* beta, float* y0, float* mean0,
+                        float* rstd0, long long rows, int K0, int l2, float eps_ln, float eps_l2, float p_drop,
+                        unsigned long long seed, void* stream);
+size_t stage_feat16_ln_bwd_ws_bytes(int K0);
+int stage_feat16_ln_bwd(const float* dy0, const void* x, int dtype, const int* src_rows, const float* mean0, const float* rstd0,
+                        float* dgamma, float* dbeta, long long rows, int K0, int l2, float eps_l2, float p_drop,
+                        unsigned long long seed, void* ws, size_t ws_bytes, void* stream);
+/* G1 / its ragged form on half-precision features (model/stage.py:350-362 as stage_grp_input_mlp_*): the first stage above, then the
+ * unchanged Linear / LayerNorm chain.  Same params / grads / seeds / flags; the arena holds no normalised image (its size does not depend
+ * on l2); the backward scratch is stage_grp_input_mlp_bwd_tmp_bytes.  src_rows as in stage_grp_input_mlp_rag_*. */
+size_t stage_grp_input_mlp_h_arena_bytes(long long M, int K0, int H, int D);
+int stage_grp_input_mlp_h_fwd(const void* x, int dtype, const float* const* params, float* out, void* arena, size_t arena_bytes,
+                              int* flags, long long M, int K0, int H, int D, int l2, float p_drop, const unsigned long long* seeds,
+                              void* stream);
+int stage_grp_input_mlp_h_bwd(const float* dout, const void* x, int dtype, const float* const* params, float* const* grads,
+                              const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M,
+                              int K0, int H, int D, int l2, float p_drop, const unsigned long long* seeds, void* stream);
+int stage_grp_input_mlp_rag_h_fwd(const void* x, int dtype, const int* src_rows, const float* const* params, float* out, void* arena,
+                                  size_t arena_bytes, int* flags, long long M, int K0, int H, int D, int l2, float p_drop,
+                                  const unsigned long long* seeds, void* stream);
+int stage_grp_input_mlp_rag_h_bwd(const float* dout, const void* x, int dtype, const int* src_rows, const float* const* params,
+                                  float* const* grads, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
+                                  size_t tmp_bytes, long long M, int K0, int H, int D, int l2, float p_drop,
+                                  const unsigned long long* seeds, void* stream);
 int stage_rag_fill_pooled(float* out, int* argmax, long long rows, int D, void* stream);      /* -1e10 / 0: model/stage.py:503 on an all-masked group */
 int stage_rag_zero_dump(float* A_fc, const int* fmap, int N, int NA, int Li, int Lqa, int D, void* stream);
 /* K1 with a frame-compact A / dA (model/context_query_attention.py:35-101; D == 128, the fast kernels only) */

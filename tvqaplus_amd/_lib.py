@@ -154,6 +154,16 @@ SIGNATURES = {
     "stage_l2norm_gather_fwd": (I, [P, P, P, LL, I, F, P]),
     "stage_grp_input_mlp_rag_fwd": (I, [P, P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
     "stage_grp_input_mlp_rag_bwd": (I, [P, P, P, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
+    # half-precision feature rows in the fp32 model (csrc/feat16.hip): first stage of the input MLP, and G1 / its ragged form on it
+    "stage_feat16_supported": (I, [I, I]),
+    "stage_feat16_ln_fwd": (I, [P, I, P, P, P, P, P, P, LL, I, I, F, F, F, U64, P]),
+    "stage_feat16_ln_bwd_ws_bytes": (SZ, [I]),
+    "stage_feat16_ln_bwd": (I, [P, P, I, P, P, P, P, P, LL, I, I, F, F, U64, P, SZ, P]),
+    "stage_grp_input_mlp_h_arena_bytes": (SZ, [LL, I, I, I]),
+    "stage_grp_input_mlp_h_fwd": (I, [P, I, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
+    "stage_grp_input_mlp_h_bwd": (I, [P, P, I, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
+    "stage_grp_input_mlp_rag_h_fwd": (I, [P, I, P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
+    "stage_grp_input_mlp_rag_h_bwd": (I, [P, P, I, P, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
     "stage_cat3_ln_gemm_fwd_rag_supported": (I, [LL, LL, LL, I]),
     "stage_cat3_ln_gemm_fwd_rag": (I, [P, P, P, P, P, P, P, P, P, P, P, P, LL, LL, LL, I, F, F, U64, P, SZ, P]),
     "stage_cat3_dx_ln_bwd_rag_supported": (I, [LL, LL, I, I, I, I]),
@@ -215,6 +225,8 @@ def load() -> ctypes.CDLL:
     _lib = lib
     return lib
 
+
+STAGE_DT_F16, STAGE_DT_BF16 = 1, 2     # include/stage_hip.h: dtype codes of the half-precision feature entry points
 
 STAGE_ERR_SHAPE = -1      # include/stage_hip.h
 STAGE_ERR_WORKSPACE = -2

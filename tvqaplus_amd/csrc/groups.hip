@@ -238,6 +238,66 @@ int input_mlp_bwd(const float* dout, const float* x, const int* gather, const fl
 }
 }  // namespace
 
+// G1 on HALF-PRECISION features (csrc/feat16.hip): x holds fp16 / bf16 rows that the first stage reads in place -- no fp32 image, and
+// with l2 no normalised image either (the arena is the l2 == 0 layout: xn is never carved); behind the first stage, the chain above.
+extern "C" size_t stage_grp_input_mlp_h_arena_bytes(long long M, int K0, int H, int D) { return mlp_layout(nullptr, M, K0, H, D, 0).bytes; }
+
+namespace {
+bool input_mlp_h_ok(const void* x, int dtype, long long M, int K0, int H, int D) {
+    return M > 0 && M < (1ll << 31) && H % 4 == 0 && D % 4 == 0 && H > 0 && D > 0 && H <= 1024 && D <= 1024 &&
+           stage_feat16_supported(K0, dtype) && x && ((uintptr_t)x & 7) == 0;
+}
+int input_mlp_h_fwd(const void* x, int dtype, const int* gather, const float* const* P, float* out, void* arena, size_t arena_bytes,
+                    int* flags, long long M, int K0, int H, int D, int l2, float p, const unsigned long long* seeds, void* st) {
+    if (!input_mlp_h_ok(x, dtype, M, K0, H, D)) return STAGE_ERR_SHAPE;
+    MlpArena a = mlp_layout(arena, M, K0, H, D, 0);
+    if (arena_bytes < a.bytes) return STAGE_ERR_WORKSPACE;
+    TRY(stage_feat16_ln_fwd(x, dtype, gather, P[0], P[1], a.y0, a.mean0, a.rstd0, M, K0, l2, EPS_LN, EPS_L2, p, seeds[0], st));
+    TRY(lin_fwd(a.y0, P[2], P[3], a.h1, a.mask1, &flags[0], M, H, K0, 1, st));
+    TRY(stage_layernorm_fwd(a.h1, nullptr, 0, nullptr, P[4], P[5], a.y1, a.mean1, a.rstd1, M, H, EPS_LN, p, seeds[1], st));
+    TRY(lin_fwd(a.y1, P[6], P[7], a.h2, a.mask2, &flags[1], M, D, H, 1, st));
+    TRY(stage_layernorm_fwd(a.h2, nullptr, 0, nullptr, P[8], P[9], out, a.mean2, a.rstd2, M, D, EPS_LN, 0.f, 0ull, st));
+    return 0;
+}
+int input_mlp_h_bwd(const float* dout, const void* x, int dtype, const int* gather, const float* const* P, float* const* G,
+                    const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M, int K0, int H, int D,
+                    int l2, float p, const unsigned long long* seeds, void* st) {
+    if (!input_mlp_h_ok(x, dtype, M, K0, H, D)) return STAGE_ERR_SHAPE;
+    MlpArena a = mlp_layout((void*)arena, M, K0, H, D, 0);
+    MlpTmp t = mlp_tmp(tmp, M, K0, H, D);
+    if (arena_bytes < a.bytes || tmp_bytes < t.bytes || t.wsb < stage_feat16_ln_bwd_ws_bytes(K0)) return STAGE_ERR_WORKSPACE;
+    TRY(stage_layernorm_bwd(dout, a.h2, a.mean2, a.rstd2, P[8], t.dh2, nullptr, G[8], G[9], M, D, 0.f, 0ull, t.ws, stage_ln_bwd_ws_bytes(D), st));
+    TRY(lin_bwd(t.dh2, a.y1, a.h2, a.mask2, flags[1], 1, P[6], t.wt, t.dy1, G[6], G[7], M, D, H, t.ws, t.wsb, st));
+    TRY(stage_layernorm_bwd(t.dy1, a.h1, a.mean1, a.rstd1, P[4], t.dh1, nullptr, G[4], G[5], M, H, p, seeds[1], t.ws, stage_ln_bwd_ws_bytes(H), st));
+    TRY(lin_bwd(t.dh1, a.y0, a.h1, a.mask1, flags[0], 1, P[2], t.wt, t.dy0, G[2], G[3], M, H, K0, t.ws, t.wsb, st));
+    return stage_feat16_ln_bwd(t.dy0, x, dtype, gather, a.mean0, a.rstd0, G[0], G[1], M, K0, l2, EPS_L2, p, seeds[0], t.ws,
+                               stage_feat16_ln_bwd_ws_bytes(K0), st);
+}
+}  // namespace
+extern "C" int stage_grp_input_mlp_h_fwd(const void* x, int dtype, const float* const* P, float* out, void* arena, size_t arena_bytes,
+                                         int* flags, long long M, int K0, int H, int D, int l2, float p,
+                                         const unsigned long long* seeds, void* st) {
+    return input_mlp_h_fwd(x, dtype, nullptr, P, out, arena, arena_bytes, flags, M, K0, H, D, l2, p, seeds, st);
+}
+extern "C" int stage_grp_input_mlp_h_bwd(const float* dout, const void* x, int dtype, const float* const* P, float* const* G,
+                                         const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes,
+                                         long long M, int K0, int H, int D, int l2, float p, const unsigned long long* seeds, void* st) {
+    return input_mlp_h_bwd(dout, x, dtype, nullptr, P, G, arena, arena_bytes, flags, tmp, tmp_bytes, M, K0, H, D, l2, p, seeds, st);
+}
+extern "C" int stage_grp_input_mlp_rag_h_fwd(const void* x, int dtype, const int* src_rows, const float* const* P, float* out,
+                                             void* arena, size_t arena_bytes, int* flags, long long M, int K0, int H, int D, int l2,
+                                             float p, const unsigned long long* seeds, void* st) {
+    if (!src_rows) return STAGE_ERR_SHAPE;
+    return input_mlp_h_fwd(x, dtype, src_rows, P, out, arena, arena_bytes, flags, M, K0, H, D, l2, p, seeds, st);
+}
+extern "C" int stage_grp_input_mlp_rag_h_bwd(const float* dout, const void* x, int dtype, const int* src_rows, const float* const* P,
+                                             float* const* G, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
+                                             size_t tmp_bytes, long long M, int K0, int H, int D, int l2, float p,
+                                             const unsigned long long* seeds, void* st) {
+    if (!src_rows) return STAGE_ERR_SHAPE;
+    return input_mlp_h_bwd(dout, x, dtype, src_rows, P, G, arena, arena_bytes, flags, tmp, tmp_bytes, M, K0, H, D, l2, p, seeds, st);
+}
+
 // =====================================================================================================================
 // G2  encoder block without self-attention (model/encoder.py:29-52, model/cnn.py:37-47, model/position_encoding.py:38-43):
 //     x + pe -> n_conv x [LN (+dropout on even i) -> depthwise conv -> 1x1 conv + ReLU -> + residual] -> final LN

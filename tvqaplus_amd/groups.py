@@ -10,7 +10,7 @@ paths equal, dropout on): what changes is that the step no longer depends on how
 Memory: the caller (this module) owns everything.  ``arena`` = one buffer per group call that the C side carves into what the
 backward needs; ``tmp`` = backward-only scratch, freed when the backward returns (stream-ordered, like every torch temporary).
 A group that does not take a shape raises ``Unsupported`` BEFORE launching anything; STAGE then runs that group per-op.
-fp32 storage only (the bf16 storage mode stays on the per-op path).
+fp32 storage only (the bf16 storage mode stays on the per-op path); the input MLP also takes fp16 / bf16 FEATURES (``feat16_ok``).
 """
 from __future__ import annotations
 
@@ -174,23 +174,51 @@ def gate(params: Sequence[torch.Tensor]) -> List[torch.Tensor]:
 # ---------------------------------------------------------------------------------------------------------------
 # G1 input MLP
 # ---------------------------------------------------------------------------------------------------------------
+_HALF = {torch.float16: _lib.STAGE_DT_F16, torch.bfloat16: _lib.STAGE_DT_BF16}
+
+
+def feat16_ok(x) -> bool:
+    """fp16 / bf16 features the input-MLP groups read IN PLACE (csrc/feat16.hip): a width the kernels take, contiguous rows, an
+    8-byte aligned base.  Anything else is upcast by the caller (STAGE.base_encoder) and runs the fp32 entry points."""
+    code = _HALF.get(x.dtype)
+    return (code is not None and x.is_cuda and x.dim() >= 1 and x.numel() > 0 and x.is_contiguous() and x.data_ptr() % 8 == 0
+            and bool(_lib.load().stage_feat16_supported(int(x.shape[-1]), code)))
+
+
+def _features(x):
+    """-> (x, dtype code): float32 features (code 0: the fp32 entry points), or half-precision ones as they are (never a copy)."""
+    if x.dtype in _HALF:
+        if not feat16_ok(x):
+            raise Unsupported("half-precision features: width, alignment or layout")
+        return x, _HALF[x.dtype]
+    return _chk(x, "x"), 0
+
+
 class _InputMLP(torch.autograd.Function):
     @_on_device
     def forward(ctx, x, l2: int, p: float, seeds, *params):
-        x = _chk(x, "x")
+        x, half = _features(x)
         ctx.sinks = _sinks(params)
         params = _params(params)
         K0, H, D = x.shape[-1], params[2].shape[0], params[6].shape[0]
         M = x.numel() // K0
         lib = _lib.load()
-        ab = _size("stage_grp_input_mlp_arena_bytes", M, K0, H, D, int(l2))
+        if half:
+            ab = _size("stage_grp_input_mlp_h_arena_bytes", M, K0, H, D)
+        else:
+            ab = _size("stage_grp_input_mlp_arena_bytes", M, K0, H, D, int(l2))
         arena = _buf(ab, x.device)
         out = torch.empty(x.shape[:-1] + (D,), dtype=torch.float32, device=x.device)
         flags = _flags()
-        _rc(lib.stage_grp_input_mlp_fwd(x.data_ptr(), _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags, M, K0, H, D, int(l2),
-                                        float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_fwd")
-        ctx.save_for_backward(x, arena, *params)
+        if half:
+            _rc(lib.stage_grp_input_mlp_h_fwd(x.data_ptr(), half, _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags, M, K0, H, D,
+                                              int(l2), float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_h_fwd")
+        else:
+            _rc(lib.stage_grp_input_mlp_fwd(x.data_ptr(), _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags, M, K0, H, D, int(l2),
+                                            float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_fwd")
+        ctx.save_for_backward(x, arena, *params)      # (half-precision features: the caller's tensor itself)
         ctx.cfg = (M, K0, H, D, int(l2), float(p), tuple(seeds), flags, ab)
+        ctx.half = half
         return out
 
     @_on_device
@@ -202,13 +230,20 @@ class _InputMLP(torch.autograd.Function):
         grads = _grad_views(params)
         tb = _size("stage_grp_input_mlp_bwd_tmp_bytes", M, K0, H, D)
         tmp = _buf(tb, x.device)
-        _rc(lib.stage_grp_input_mlp_bwd(dout.data_ptr(), x.data_ptr(), _ptrs(params), _ptrs(grads), arena.data_ptr(), ab, flags,
-                                        tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()), "stage_grp_input_mlp_bwd")
+        if ctx.half:
+            _rc(lib.stage_grp_input_mlp_h_bwd(dout.data_ptr(), x.data_ptr(), ctx.half, _ptrs(params), _ptrs(grads), arena.data_ptr(), ab,
+                                              flags, tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()),
+                "stage_grp_input_mlp_h_bwd")
+        else:
+            _rc(lib.stage_grp_input_mlp_bwd(dout.data_ptr(), x.data_ptr(), _ptrs(params), _ptrs(grads), arena.data_ptr(), ab, flags,
+                                            tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()), "stage_grp_input_mlp_bwd")
         return (None, None, None, None) + _deliver(ctx.sinks, grads)
 
 
 def input_mlp(x, l2: bool, p: float, seeds, params):
-    """x (..., K0) features -> (..., D).  params: ln0.w ln0.b fc1.w fc1.b ln1.w ln1.b fc2.w fc2.b ln2.w ln2.b."""
+    """x (..., K0) features -> (..., D).  params: ln0.w ln0.b fc1.w fc1.b ln1.w ln1.b fc2.w fc2.b ln2.w ln2.b.
+    x: float32, or float16 / bfloat16 that ``feat16_ok`` accepts -- read in place and converted in registers (csrc/feat16.hip): the
+    result is that of ``x.float()``, no fp32 copy of the features exists, and the backward re-reads the same tensor."""
     return _InputMLP.apply(x, int(bool(l2)), p, tuple(seeds), *params)
 
 
@@ -436,21 +471,30 @@ def encoder_block_rag(x, pe, qa_mask, lay, k: int, p: float, seeds, params):
 class _InputMLPRag(torch.autograd.Function):
     @_on_device
     def forward(ctx, x, clay, l2: int, p: float, seeds, *params):
-        x = _chk(x, "x")                       # the padded feature tensor, (..., K0)
+        x, half = _features(x)                 # the padded feature tensor, (..., K0)
         ctx.sinks = _sinks(params)
         params = _params(params)
         K0, H, D = x.shape[-1], params[2].shape[0], params[6].shape[0]
         M = clay.U
         lib = _lib.load()
-        ab = _size("stage_grp_input_mlp_arena_bytes", clay.Ucap, K0, H, D, int(l2))
+        if half:
+            ab = _size("stage_grp_input_mlp_h_arena_bytes", clay.Ucap, K0, H, D)
+        else:
+            ab = _size("stage_grp_input_mlp_arena_bytes", clay.Ucap, K0, H, D, int(l2))
         arena = _buf(ab, x.device)
         out = _rows(M, D, x.device)
         flags = _flags()
-        _rc(lib.stage_grp_input_mlp_rag_fwd(x.data_ptr(), clay.src_rows.data_ptr(), _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags,
-                                            M, K0, H, D, int(l2), float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_rag_fwd")
+        if half:
+            _rc(lib.stage_grp_input_mlp_rag_h_fwd(x.data_ptr(), half, clay.src_rows.data_ptr(), _ptrs(params), out.data_ptr(), arena.data_ptr(),
+                                                  ab, flags, M, K0, H, D, int(l2), float(p), _u64(seeds), _stream()),
+                "stage_grp_input_mlp_rag_h_fwd")
+        else:
+            _rc(lib.stage_grp_input_mlp_rag_fwd(x.data_ptr(), clay.src_rows.data_ptr(), _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags,
+                                                M, K0, H, D, int(l2), float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_rag_fwd")
         ctx.save_for_backward(x, arena, *params)
         ctx.cfg = (M, K0, H, D, int(l2), float(p), tuple(seeds), flags, ab)
         ctx.clay = clay
+        ctx.half = half
         return out
 
     @_on_device
@@ -462,15 +506,20 @@ class _InputMLPRag(torch.autograd.Function):
         grads = _grad_views(params)
         tb = _size("stage_grp_input_mlp_bwd_tmp_bytes", ctx.clay.Ucap, K0, H, D)
         tmp = _buf(tb, x.device)
-        _rc(lib.stage_grp_input_mlp_rag_bwd(dout.data_ptr(), x.data_ptr(), ctx.clay.src_rows.data_ptr(), _ptrs(params), _ptrs(grads),
-                                            arena.data_ptr(), ab, flags, tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()),
-            "stage_grp_input_mlp_rag_bwd")
+        if ctx.half:
+            _rc(lib.stage_grp_input_mlp_rag_h_bwd(dout.data_ptr(), x.data_ptr(), ctx.half, ctx.clay.src_rows.data_ptr(), _ptrs(params),
+                                                  _ptrs(grads), arena.data_ptr(), ab, flags, tmp.data_ptr(), tb, M, K0, H, D, l2, p,
+                                                  _u64(seeds), _stream()), "stage_grp_input_mlp_rag_h_bwd")
+        else:
+            _rc(lib.stage_grp_input_mlp_rag_bwd(dout.data_ptr(), x.data_ptr(), ctx.clay.src_rows.data_ptr(), _ptrs(params), _ptrs(grads),
+                                                arena.data_ptr(), ab, flags, tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()),
+                "stage_grp_input_mlp_rag_bwd")
         return (None, None, None, None, None) + _deliver(ctx.sinks, grads)
 
 
 def input_mlp_rag(x, clay, l2: bool, p: float, seeds, params):
     """As ``input_mlp`` on the compact rows of a ragged context stream: x the padded (..., K0) features, ``clay.src_rows`` the rows of it
-    that exist; -> (clay.U, D)."""
+    that exist; -> (clay.U, D).  Half-precision x: as ``input_mlp``."""
     return _InputMLPRag.apply(x, clay, int(bool(l2)), p, tuple(seeds), *params)
 
 

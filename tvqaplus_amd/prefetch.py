@@ -13,6 +13,11 @@ Non-tensor fields (qid lists, att_labels, boxes, ...) pass through untouched.
 ``feature_dtype=torch.bfloat16`` (for a model built with ``opt.storage_dtype = "bf16"``) rounds the three feature tensors
 (``qas_bert``, ``sub_bert``, ``vid``) to bf16 while they are copied into the pinned staging buffers: the model would round them
 on entry anyway, and the transfer is 431 MB instead of 862 MB.  Masks, labels and indices keep their types.
+
+``feature_dtype=torch.float16`` or ``torch.bfloat16`` is equally valid for the default fp32 model: its input MLP reads half-precision
+features in place and converts them in registers (csrc/feat16.hip), so the step computes exactly what it computes on
+``features.float()`` -- without an fp32 copy on the device, with the ragged context layout kept, and with half the bytes on the bus.
+What is lost is the rounding of the features themselves; datasets that store them as fp16 lose nothing.
 """
 from __future__ import annotations
 
@@ -31,8 +36,8 @@ class BatchPrefetcher:
         self.device = torch.device(device)
         self.side = torch.cuda.Stream(device=self.device)
         self.depth = max(2, int(depth))
-        if feature_dtype not in (None, torch.float32, torch.bfloat16):
-            raise ValueError("feature_dtype must be None, torch.float32 or torch.bfloat16")
+        if feature_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
+            raise ValueError("feature_dtype must be None, torch.float32, torch.float16 or torch.bfloat16")
         self.feature_dtype = feature_dtype
         self._pinned: list = [dict() for _ in range(self.depth)]   # per slot: key -> pinned staging tensor
         self._free_evt: list = [None] * self.depth                  # per slot: event after which the staging set is reusable

@@ -425,8 +425,10 @@ class STAGE(nn.Module):
             x = self._encoder_block(x, mask, blk, pool_mask=pool_mask if j == len(blocks) - 1 else None)
         return x
 
-    def base_encoder(self, data, data_mask, init_encoder, downsize_encoder, input_encoder, l2_normalize=False, clay=None):
-        """model/stage.py:350-363 (+ the F.normalize of :256 when l2_normalize)."""
+    def base_encoder(self, data, data_mask, init_encoder, downsize_encoder, input_encoder, l2_normalize=False, clay=None,
+                     feat16=True):
+        """model/stage.py:350-363 (+ the F.normalize of :256 when l2_normalize).  ``data`` may be fp16 / bf16 in the fp32 model: the
+        input-MLP group reads such features in place (``feat16``; csrc/feat16.hip), every other path upcasts them first."""
         M, L, _ = data.shape
         if clay is not None:
             # ragged context rows (tvqaplus_amd/ragged.py: CtxLayout): the MLP reads the live rows of the padded features in place,
@@ -445,6 +447,16 @@ class STAGE(nn.Module):
                 y = groups.encoder_block_rag(y, blk.position_encoding.rows(L), None, clay, k, self._p(),
                                              self._seeds((blk.n_conv + 1) // 2), [self._g(w) for w in bp])
             return y
+        if (feat16 and data.dtype in (torch.float16, torch.bfloat16) and self._grouped() and not self.fuse_input_ln
+                and groups.feat16_ok(data)):
+            # half-precision features, fp32 model: converted in registers by the group's first kernel -- no fp32 copy to keep alive
+            params = [init_encoder[0].weight, init_encoder[0].bias, init_encoder[2].weight, init_encoder[2].bias,
+                      init_encoder[4].weight, init_encoder[4].bias, downsize_encoder[1].weight, downsize_encoder[1].bias,
+                      downsize_encoder[3].weight, downsize_encoder[3].bias]
+            params = [self._g(w) for w in params]
+            y = self._try_group(lambda seeds: groups.input_mlp(data, l2_normalize, self._p(), seeds, params), 2)
+            if y is not None:
+                return self._stacked_encoder(y.view(M, L, -1), data_mask, input_encoder)
         if data.dtype != self.storage:
             data = data.to(self.storage)      # bf16 storage: features are rounded once on entry
         if self._grouped() and not self.fuse_input_ln and data.dtype == torch.float32:
@@ -752,7 +764,7 @@ class STAGE(nn.Module):
             idx_d = torch.from_numpy(idx).to(data.device, non_blocking=True)
             xb = data[:, :Lb].index_select(0, idx_d)                # (Mb, Lb, F): only these positions are read
             mb = data_mask[:, :Lb].index_select(0, idx_d)
-            yb = self.base_encoder(xb, mb, init_encoder, downsize_encoder, input_encoder, l2_normalize=l2_normalize)
+            yb = self.base_encoder(xb, mb, init_encoder, downsize_encoder, input_encoder, l2_normalize=l2_normalize, feat16=False)
             idxs.append(idx_d)
             ys.append(yb.view(len(idx), Lb, -1))
         if not ys:
@@ -821,7 +833,10 @@ class STAGE(nn.Module):
             halo = sum(ragged.conv_halo(1, b.n_conv, ik) for b in iblocks) if conv_only else 1 << 20
             for (mask, _, L), name in zip(streams, names):
                 feat = batch.sub_bert if name == "sub" else batch.vid
-                if feat.dtype != torch.float32 or feat.shape[-1] % 4 or feat.shape[-1] > 1024 or not feat.is_contiguous():
+                if feat.dtype in (torch.float16, torch.bfloat16):
+                    if not groups.feat16_ok(feat):      # (the stream then runs padded, on the upcast features)
+                        continue
+                elif feat.dtype != torch.float32 or feat.shape[-1] % 4 or feat.shape[-1] > 1024 or not feat.is_contiguous():
                     continue
                 ct = ragged.CtxTables(info[name + "_len"], int(L), halo)
                 if ct.U == 0:
