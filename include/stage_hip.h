@@ -474,6 +474,24 @@ int stage_grp_pool_cls_bwd(const float* d_logits, const float* mask, const int* 
                            float* const* grads, float* d_first, const void* arena, size_t arena_bytes, void* tmp, size_t tmp_bytes,
                            int N, int NA, int Li, int D, long long P, float p_drop, const unsigned long long* seeds, void* stream);
 
+/* G7 evaluation head (model/stage.py:440-448, 526-536 outside training; csrc/eval_head.hip): what get_proposals + the classifier do in
+ * eval()/inference for R = N * NA independent rows, forward only.  first (R, Li, D), mask (R, Li), t_scores (R, Li, 2).
+ *   span (R, 2) int32 [st, ed] = arg max over i <= j of softmax(start)[i] * softmax(end)[j], ties: smallest i * Li + j; conf (R) its
+ *   value; both may be NULL.  pooled row = [masked max over [max(0, st - extra), ed + 1 + extra) | masked max over all frames]
+ *   (local == 0: the latter only, D wide; t_scores may then be NULL unless span / conf is wanted), then LayerNorm and Linear(-> 1)
+ *   through stage_layernorm_fwd / stage_gemm_nt: logits (R).  params: ln_g ln_b W c.  O(Li) memory per row; nothing is kept.
+ * stage_eval_head_supported: 1 <= Li <= 2048, D % 4 == 0, 2 D <= 1024 (needs no GPU); elsewhere the group returns STAGE_ERR_SHAPE
+ *   before anything is launched.
+ * stage_answer_spans (inference.py:13-35 for a batch): answer (N, NA <= 64), t_prob (N, NA, Li <= 2048, 2) ALREADY softmaxed ->
+ *   out (N, 3) int32 [st, ed, answer]: answer = first arg max of the row; the span of that candidate by the sweep of
+ *   find_max_pair (start = first arg max of p_st[:i + 1], end = first position reaching the best product, (0, 1) when it is <= 0). */
+int stage_eval_head_supported(int Li, int D, int local);
+size_t stage_grp_eval_head_arena_bytes(long long R, int D, int local);
+int stage_grp_eval_head_fwd(const float* first, const float* mask, const float* t_scores, const float* const* params, float* logits,
+                            int* span, float* conf, void* arena, size_t arena_bytes, long long R, int Li, int D, int extra, int local,
+                            void* stream);
+int stage_answer_spans(const float* answer, const float* t_prob, int* out, int N, int NA, int Li, void* stream);
+
 
 /* ==== Ragged token rows: live-range execution of the (N, 5, Li, Lqa, .) kernels ===================================================
  * The reference computes every padded row of the (N,5,Li,Lqa,D) tensors (model/stage.py:365-387 qa_ctx_attention, :276-279 concat_fc,

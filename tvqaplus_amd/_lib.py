@@ -142,6 +142,11 @@ SIGNATURES = {
     "stage_grp_pool_cls_fwd": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, LL, F, P, P]),
     "stage_grp_pool_cls_bwd_tmp_bytes": (SZ, [LL, I, I]),
     "stage_grp_pool_cls_bwd": (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, F, P, P]),
+    # evaluation head (csrc/eval_head.hip; G7 in csrc/groups.hip) and the prediction writer's span decoder
+    "stage_eval_head_supported": (I, [I, I, I]),
+    "stage_grp_eval_head_arena_bytes": (SZ, [LL, I, I]),
+    "stage_grp_eval_head_fwd": (I, [P, P, P, P, P, P, P, P, SZ, LL, I, I, I, I, P]),
+    "stage_answer_spans": (I, [P, P, P, I, I, I, P]),
     # ragged token rows (csrc/ragged.hip and the *_rag / *_fc variants; include/stage_hip.h "Ragged token rows")
     "stage_rag_rowinfo": (I, [P, P, LL, I, P, P]),
     "stage_rag_fill_pooled": (I, [P, P, LL, I, P]),

@@ -85,6 +85,22 @@ __device__ __forceinline__ float cross_row_sum(float v) {
 }
 __device__ __forceinline__ float cross_row_max(float v) { return xmax32(xmax16(v)); }
 
+// block-wide reductions in a fixed order (256 threads; sh: 4 floats of LDS; csrc/groups.hip span_kernel / ts_loss_kernel, csrc/eval_head.hip)
+__device__ __forceinline__ float block_max256(float v, float* sh) {
+    v = wave_max(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
+}
+__device__ __forceinline__ float block_sum256(float v, float* sh) {
+    v = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
 // Ticket counters for dynamically distributed kernels WITHOUT a per-launch reset: a device-resident ring of 64 words that
 // only ever count up.  The host knows exactly how many tickets a launch draws (every processed item past the static rounds
 // draws one), so it hands the kernel the value its word will have when the launch starts (`base`, kernels use drawn - base in

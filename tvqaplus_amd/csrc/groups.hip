@@ -978,22 +978,7 @@ __global__ void tscores_bwd_kernel(const float* __restrict__ dout, const float* 
     d_ed[r] = g.y * m;
 }
 
-// block-wide reductions in a fixed order (256 threads)
-__device__ __forceinline__ float block_max256(float v, float* sh) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
-}
-__device__ __forceinline__ float block_sum256(float v, float* sh) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
+// (block_max256 / block_sum256, the block-wide reductions in a fixed order: common.h)
 // Span proposal of the ground-truth candidate (training; model/stage.py:408-418, model/model_utils.py:92-123): softmax over the
 // frames of its start / end scores, arg max of the upper-triangular products p_st[i] * p_ed[j] (i <= j; the first maximal pair in
 // row-major order).  One workgroup per example.  spans (6, N): st, ed, confidence, label start, label end, answer index.
@@ -1399,4 +1384,47 @@ extern "C" int stage_grp_pool_cls_bwd(const float* d_logits, const float* mask, 
                        mask, inv, d_first, Rs, NA, Li, D / 4);
     STAGE_LAUNCH_CHECK();
     return 0;
+}
+
+// ---- G7  evaluation head: span of every candidate row + windowed / global pooling + answer classifier (model/stage.py:440-448,
+//     526-536 outside training; kernels: csrc/eval_head.hip) ---------------------------------------------------------------------
+//     first (R, Li, D), mask (R, Li), t_scores (R, Li, 2), R = N * NA independent rows.  logits (R); span (R, 2) int32 [st, ed] and
+//     conf (R) may be NULL.  local == 0 (add_local = False): global pooling only, D wide; t_scores may then be NULL when neither
+//     span nor conf is wanted.  params: ln_g ln_b W c (2D wide, D wide for local == 0).  Forward only: nothing is kept.
+int stage_eval_span_launch(const float* t_scores, int* span, float* conf, int* win, long long R, int Li, int extra, void* st);
+int stage_eval_pool_launch(const float* first, const float* mask, const int* win, float* pooled, long long R, int Li, int D, int local,
+                           void* st);
+namespace {
+struct EhArena { float *pooled, *y, *mean, *rstd; int* win; size_t bytes; };
+EhArena eh_layout(void* base, long R, int W) {
+    Bump b{(char*)base, 0};
+    EhArena a;
+    a.pooled = b.take<float>((size_t)R * W);
+    a.y = b.take<float>((size_t)R * W);
+    a.mean = b.take<float>((size_t)R);
+    a.rstd = b.take<float>((size_t)R);
+    a.win = b.take<int>((size_t)R * 2);
+    a.bytes = b.off;
+    return a;
+}
+}  // namespace
+
+extern "C" size_t stage_grp_eval_head_arena_bytes(long long R, int D, int local) {
+    return eh_layout(nullptr, (long)R, local ? 2 * D : D).bytes;
+}
+
+extern "C" int stage_grp_eval_head_fwd(const float* first, const float* mask, const float* t_scores, const float* const* P,
+                                       float* logits, int* span, float* conf, void* arena, size_t arena_bytes, long long R, int Li,
+                                       int D, int extra, int local, void* st) {
+    if (!stage_eval_head_supported(Li, D, local) || R <= 0 || R > 0x7fffffffLL || extra < 0 || extra > (1 << 20)) return STAGE_ERR_SHAPE;
+    const bool want_span = local || span || conf;
+    if ((want_span && (!t_scores || ((uintptr_t)t_scores & 7))) || !al16(first)) return STAGE_ERR_SHAPE;
+    const int W = local ? 2 * D : D;
+    EhArena a = eh_layout(arena, (long)R, W);
+    if (arena_bytes < a.bytes) return STAGE_ERR_WORKSPACE;
+    if (want_span) TRY(stage_eval_span_launch(t_scores, span, conf, a.win, R, Li, extra, st));
+    TRY(stage_eval_pool_launch(first, mask, a.win, a.pooled, R, Li, D, local, st));
+    TRY(stage_layernorm_fwd(a.pooled, nullptr, 0, nullptr, P[0], P[1], a.y, a.mean, a.rstd, R, W, EPS_LN, 0.f, 0ull, st));
+    int none = 0;
+    return lin_fwd(a.y, P[2], P[3], logits, nullptr, &none, R, 1, W, 0, st);
 }

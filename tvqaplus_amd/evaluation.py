@@ -63,6 +63,19 @@ def find_max_pair_batch(p_st: torch.Tensor, p_ed: torch.Tensor) -> Tuple[torch.T
     return st, ed, val
 
 
+def _device_rows(answer: torch.Tensor, t_scores: torch.Tensor) -> Optional[torch.Tensor]:
+    """(N, 3) [st, ed, answer] from ONE kernel (``groups.answer_spans``: the decoder above, same tie rules) when both tensors are
+    fp32 on the GPU and the kernel takes the shape; None otherwise (the torch composition of ``find_max_pair_batch`` then runs)."""
+    if not (answer.is_cuda and t_scores.is_cuda and answer.dtype == torch.float32 and t_scores.dtype == torch.float32
+            and answer.dim() == 2 and t_scores.dim() == 4 and 1 <= t_scores.shape[2] <= 2048 and answer.shape[0] >= 1):
+        return None
+    from . import groups
+    try:
+        return groups.answer_spans(answer, t_scores)
+    except groups.Unsupported:
+        return None
+
+
 class PredictionWriter:
     """inference.py:42-72: per batch, the predicted answer, the (st, ed) span of the PREDICTED answer decoded from the
     softmaxed temporal scores and mapped to seconds (frames are sampled at 0.5 fps: ``st * 2 + offset``,
@@ -73,11 +86,14 @@ class PredictionWriter:
 
     def add_batch(self, outputs: Mapping[str, object], qids: Sequence[int], image_indices: Sequence[Sequence[int]]) -> None:
         answer, t_scores = outputs["answer"], outputs["t_scores"]             # (N, 5), (N, 5, Li, 2) softmaxed over Li
-        pred = answer.detach().max(1)[1]                                       # (N,)
-        N, _, Li, _ = t_scores.shape
-        picked = t_scores.detach().gather(1, pred.view(N, 1, 1, 1).expand(N, 1, Li, 2)).squeeze(1)    # (N, Li, 2)
-        st, ed, _ = find_max_pair_batch(picked[:, :, 0], picked[:, :, 1])
-        rows = torch.stack([st, ed, pred], dim=1).cpu().tolist()               # ONE copy per batch
+        rows = _device_rows(answer, t_scores)
+        if rows is None:
+            pred = answer.detach().max(1)[1]                                   # (N,)
+            N, _, Li, _ = t_scores.shape
+            picked = t_scores.detach().gather(1, pred.view(N, 1, 1, 1).expand(N, 1, Li, 2)).squeeze(1)    # (N, Li, 2)
+            st, ed, _ = find_max_pair_batch(picked[:, :, 0], picked[:, :, 1])
+            rows = torch.stack([st, ed, pred], dim=1)
+        rows = rows.cpu().tolist()                                             # ONE copy per batch
         if outputs.get("att_predictions"):
             self.predictions["raw_bbox"] += outputs["att_predictions"]
         for qid, (s, e, a), img in zip(qids, rows, image_indices):

@@ -848,3 +848,60 @@ def att_hard_negatives(scores, row_off, negbits, slot_begin, slot_q, out):
                                                  slot_q.data_ptr(), K, M, Lr, s.numel(), out.data_ptr(), _stream()),
             "stage_att_hard_negatives")
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# Evaluation head (csrc/eval_head.hip; G7 in csrc/groups.hip) and the prediction writer's span decoder: forward only
+# ---------------------------------------------------------------------------------------------------------------
+def eval_head_supported(Li: int, D: int, local: bool = True) -> bool:
+    """1 <= Li <= 2048, D % 4 == 0, 2 D <= 1024 (answers without a GPU)."""
+    return bool(_lib.load().stage_eval_head_supported(int(Li), int(D), int(bool(local))))
+
+
+def eval_head(first, mask, t_scores, extra: int, local, params):
+    """get_proposals + classifier outside training (model/stage.py:440-448, 526-536) for R independent rows, in one call and O(Li)
+    memory per row: first (R, Li, D), mask (R, Li), t_scores (R, Li, 2) -> (logits (R, 1), span (R, 2) int32 [st, ed], conf (R)).
+    span = arg max over i <= j of softmax(start)[i] * softmax(end)[j] (ties: smallest i * Li + j, as ``STAGE._best_span``); the row
+    is pooled over [max(0, st - extra), ed + 1 + extra) and over all frames, then LayerNorm + Linear(-> 1).  ``local`` false
+    (add_local = False): global pooling only, params D wide; ``t_scores`` may then be None (span and conf come back None).
+    params: ln.w ln.b fc.w fc.b.  No autograd node is built.  Raises ``Unsupported`` before launching anything."""
+    first, mask = _chk(first.detach(), "first"), _chk(mask.detach(), "mask")
+    R, Li, D = first.shape
+    local = int(bool(local))
+    if R < 1 or mask.numel() != R * Li or not eval_head_supported(Li, D, local):
+        raise Unsupported("stage_grp_eval_head_fwd: R = %d, Li = %d, D = %d" % (R, Li, D))
+    if t_scores is None and local:
+        raise ValueError("eval_head: the local window needs t_scores")
+    dev = first.device
+    span = conf = None
+    if t_scores is not None:
+        t_scores = _chk(t_scores.detach(), "t_scores")
+        if t_scores.numel() != R * Li * 2:
+            raise ValueError("eval_head: t_scores must hold (R, Li, 2) values")
+        span = torch.empty(R, 2, dtype=torch.int32, device=dev)
+        conf = torch.empty(R, dtype=torch.float32, device=dev)
+    params = _params([w.detach() for w in params])
+    ab = _size("stage_grp_eval_head_arena_bytes", R, D, local)
+    arena = _buf(ab, dev)
+    logits = torch.empty(R, 1, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _rc(_lib.load().stage_grp_eval_head_fwd(first.data_ptr(), mask.data_ptr(), None if t_scores is None else t_scores.data_ptr(),
+                                                _ptrs(params), logits.data_ptr(), None if span is None else span.data_ptr(),
+                                                None if conf is None else conf.data_ptr(), arena.data_ptr(), ab, R, Li, D, int(extra),
+                                                local, _stream()), "stage_grp_eval_head_fwd")
+    return logits, span, conf
+
+
+def answer_spans(answer, t_prob):
+    """The prediction writer's decoder on the device (inference.py:13-35; ``evaluation.find_max_pair_batch`` is the specification):
+    answer (N, NA <= 64), t_prob (N, NA, Li <= 2048, 2) softmaxed over Li -> (N, 3) int32 [st, ed, predicted answer]."""
+    answer, t_prob = _chk(answer.detach(), "answer"), _chk(t_prob.detach(), "t_prob")
+    N, NA = answer.shape
+    Li = t_prob.shape[2]
+    if tuple(t_prob.shape) != (N, NA, Li, 2):
+        raise ValueError("answer_spans: t_prob must be (N, NA, Li, 2)")
+    out = torch.empty(N, 3, dtype=torch.int32, device=answer.device)
+    with torch.cuda.device(answer.device):
+        _rc(_lib.load().stage_answer_spans(answer.data_ptr(), t_prob.data_ptr(), out.data_ptr(), N, NA, Li, _stream()),
+            "stage_answer_spans")
+    return out

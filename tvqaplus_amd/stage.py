@@ -638,6 +638,16 @@ class STAGE(nn.Module):
             tm = ts_labels_mask.view(N, 1, Li, 1)
             t_scores = t_scores * tm + (1 - tm) * NEG                                    # :521 mask_logits
         first = first.view(N, NA, Li, D)
+        cl = self.classifier
+        if (grouped_tail and not self.training and first.is_cuda and not (torch.is_grad_enabled() and (
+                first.requires_grad or any(w.requires_grad for w in cl.parameters())))):
+            # eval() / inference without a gradient: get_proposals for every candidate row + classifier as ONE group (G7).  Rows are
+            # independent, so any NA (candidate-sharded batches) is taken; a declined shape falls through to the branches below.
+            logits = self._try_group(lambda seeds: groups.eval_head(
+                first.view(N * NA, Li, D), mx_mask.view(N * NA, Li), t_scores if self.add_local else None, extra_span_length,
+                self.add_local, [cl.conv[0].weight, cl.conv[0].bias, cl.conv[2].weight, cl.conv[2].bias])[0], 1)
+            if logits is not None:
+                return logits.view(-1, NA), targets, t_scores
         if (grouped_tail and self.add_local and self.training and gt_scores_fn is None and NA == self.num_a
                 and first.is_cuda):
             logits, targets = self._proposals_grouped(first, mx_mask, t_scores, targets, ts_labels, extra_span_length)
