@@ -641,6 +641,27 @@ int stage_grp_encoder_rag_bwd(const float* dout, const float* qa_mask, const flo
                               size_t tmp_bytes, long long U, long long Ucap, long long S, long long Rd, int Lqa, int D, int n_conv,
                               int k, float p, const unsigned long long* seeds, void* stream);
 
+/* ---- Flat Adam (main.py:63-66: clip_grad_norm_(model.parameters(), 10) + optimizer.step() with torch.optim.Adam) ----------------
+ * The clip and the Adam update on the packed gradient buffer (csrc/flat_adam.hip; tvqaplus_amd/optim.py: FlatAdam): ONE call, two
+ * launches on `stream`, no float atomics (fixed summation order: bitwise repeatable) and no device read-back.
+ *   flat, m, v   (total) fp32, 16-byte aligned: the gradients of all parameters back to back, and Adam's two moments in the same layout
+ *   seg_table    (n_seg, 3) int64 ON THE DEVICE: address of the parameter's data, its start offset in flat, its numel
+ *   chunk_table  (n_chunk, 3) int32 ON THE DEVICE: segment, offset inside the segment, length -- at most 1024 consecutive elements of
+ *                one segment per chunk, together tiling every segment (a chunk that does not fit its segment / flat is skipped)
+ *   step         (n_seg) fp32: Adam's step count per parameter; active (n_seg) bytes: non-zero = the parameter has a gradient in this
+ *                step.  An inactive parameter, its moments and its step are not touched (torch.optim.Adam skips grad = None)
+ *   betas_host   HOST array {beta1, beta2} as double (the one host pointer of the call), read before it returns: 1 - beta and the bias corrections 1 - beta^t are formed in
+ *                double as torch forms them (from a float beta2 = 0.999 they would be off by 5e-5); lr, eps, weight_decay, max_norm are
+ *                used in fp32 and travel by value
+ *   max_norm     > 0: flat is scaled by min(1, max_norm / (norm + 1e-6)) before the update and keeps the scaled values (what
+ *                clip_grad_norm_ leaves in p.grad); <= 0: no clip, flat is only read.  weight_decay is Adam's L2 form (g + wd * p)
+ *   norm_out     one float: the 2-norm of flat as the call found it; ws from stage_flat_adam_ws_bytes(total) (answers without a GPU)
+ * STAGE_ERR_SHAPE: a NULL pointer, total <= 0, n_seg <= 0, n_chunk <= 0 (nothing to update), misaligned flat / m / v.               */
+size_t stage_flat_adam_ws_bytes(long long total);
+int stage_flat_adam_step(float* flat, float* m, float* v, const long long* seg_table, int n_seg, const int* chunk_table,
+                         int n_chunk, float* step, const unsigned char* active, long long total, float lr, const double* betas_host,
+                         float eps, float weight_decay, float max_norm, void* ws, size_t ws_bytes, float* norm_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -192,6 +192,9 @@ SIGNATURES = {
     "stage_grp_encoder_rag_bwd_tmp_bytes": (SZ, [LL, I, I]),
     "stage_grp_encoder_rag_fwd": (I, [P, P, P, P, P, P, P, SZ, P, LL, LL, LL, LL, I, I, I, I, F, P, P]),
     "stage_grp_encoder_rag_bwd": (I, [P, P, P, P, P, P, P, SZ, P, P, SZ, LL, LL, LL, LL, I, I, I, I, F, P, P]),
+    # clip + Adam on the packed gradient buffer (csrc/flat_adam.hip; tvqaplus_amd/optim.py): betas is a HOST array of two doubles
+    "stage_flat_adam_ws_bytes": (SZ, [LL]),
+    "stage_flat_adam_step": (I, [P, P, P, P, I, P, I, P, P, LL, F, P, F, F, F, P, SZ, P, P]),
 }
 
 ABI_VERSION = 5    # include/stage_hip.h: STAGE_HIP_ABI_VERSION (tests/test_abi.py holds the two together)
