@@ -132,7 +132,8 @@ class RaggedTables:
         return out
 
     def rowinfo_host(self) -> np.ndarray:
-        """What stage_rag_rowinfo computes on the device."""
+        """What stage_rag_rowinfo computes on the device (held to it, row for row, by
+        tests/test_hip_ragged_kernels.py::test_rowinfo_on_the_device_equals_the_host_restatement)."""
         out = np.empty((self.U, 4), dtype=np.int32)
         for s in range(self.S):
             start, ln, g, dense = (int(v) for v in self.seq[s])
@@ -230,7 +231,8 @@ class CtxTables:
         self.seq = np.stack([qstart[live], qlen[live], np.zeros(self.S, np.int64), np.zeros(self.S, np.int64)], axis=1).astype(np.int32)
 
     def src_rows_host(self) -> np.ndarray:
-        """What stage_rag_ctx_rows computes on the device (tests)."""
+        """What stage_rag_ctx_rows computes on the device (held to it, row for row, by
+        tests/test_hip_ragged_kernels.py::test_ctx_rows_on_the_device_equal_the_host_restatement)."""
         out = np.empty(self.U, dtype=np.int32)
         for f in range(self.cq.shape[0]):
             s, n = int(self.cq[f, 0]), int(self.cq[f, 1])
