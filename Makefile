@@ -8,7 +8,7 @@ FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wno-unused-value
 
 all: $(LIB)
 
-build/%.o: tvqaplus_amd/csrc/%.hip tvqaplus_amd/csrc/common.h include/stage_hip.h
+build/%.o: tvqaplus_amd/csrc/%.hip tvqaplus_amd/csrc/common.h tvqaplus_amd/csrc/head_shared.h include/stage_hip.h
 	@mkdir -p build
 	$(HIPCC) $(FLAGS) -c $< -o $@
 

@@ -662,6 +662,47 @@ int stage_flat_adam_step(float* flat, float* m, float* v, const long long* seg_t
                          int n_chunk, float* step, const unsigned char* active, long long total, float lr, const double* betas_host,
                          float eps, float weight_decay, float max_norm, void* ws, size_t ws_bytes, float* norm_out, void* stream);
 
+/* ---- Run meter (main.py:69-74, 90-94 training statistics; :173-183 validate(); eval/eval_tvqa_plus.py:14-69 temporal metrics) -----
+ * The per-step bookkeeping of the caller's loop, accumulated in device memory (csrc/meter.hip; tvqaplus_amd/meter.py: RunMeter): every
+ * call is ONE launch of one 256-thread workgroup, stream-ordered, no atomics, no read-back.  The caller reads the statistics by copying
+ * the buffer to the host whenever it logs.  A METER BELONGS TO ONE STREAM: calls on it are ordered by that stream only.
+ *
+ * The buffer is caller-owned, 8-byte aligned, stage_meter_bytes(ring_cap) bytes, plain arrays (no struct crosses the ABI):
+ *   byte   0  double f[8]      0 loss_sum  1 cls_sum  2 att_sum  3 ts_sum  4 grad_norm_sum  5 grad_norm_max  6 iou_sum  7 reserved
+ *   byte  64  long long i[24]  0 steps  1 rows  2 correct  3 nonfinite_steps  4 ring_cursor (ring rows written)  5 ring_dropped
+ *                              6 span_rows  7 span_right  8 asa (right and IoU >= 0.5)  9..17 recall bins IoU >= 0.1 .. 0.9
+ *                              18 grad_norm_steps  19..23 reserved
+ *   byte 256  ring: ring_cap rows of 2 bytes in arrival order, one 16-bit word each: bits 0-14 the predicted index, bit 15 the
+ *             correct flag
+ * Sums: each value is widened to double and added with one IEEE addition per call (bitwise repeatable).
+ *
+ * stage_meter_bytes needs no GPU (0 for ring_cap < 0).  stage_meter_reset: asynchronous zero fill of the whole buffer.
+ * stage_meter_update: every pointer but `meter` may be NULL, its part is then skipped (P = 0 with NULL logits: the grad-norm-only call).
+ *   logits (P, C <= 4096) + targets (P) int64: prediction = the first index holding a NaN if the row has one, else the first index of
+ *     the maximum (what outputs.max(1)[1] gives on the host); correct = (prediction == target), so a negative or too-large target is
+ *     never correct but counts in rows.  Ring rows at or beyond ring_cap are not written and counted in ring_dropped.
+ *   loss, cls, att, ts, grad_norm: one device float each; att / ts are multiplied by att_w / ts_w in fp32 first (main.py:55-56).
+ *     steps += 1 when any of loss / cls / att / ts is given; nonfinite_steps += !isfinite(loss[0]).
+ * stage_train_loss_meter: stage_train_loss (same arguments, the same bits in loss and dlogits) and, in the same launch, the update with
+ *   loss = its own loss, cls = ce * scale, att = att_w * att_loss[0], ts = ts_w * t_loss[0] on its own logits / targets.
+ * stage_meter_spans: stage_answer_spans' decode (same limits: NA <= 64, Li <= 2048) of answer (N, NA) / t_prob (N, NA, Li, 2), then in
+ *   double, with gt (N, 3) ON THE DEVICE = ground-truth start, end (seconds) and the offset (image_indices[0] % 6) / 3: predicted span
+ *   [st * 2 + offset, (ed + 1) * 2 + offset] (inference.py:42-72), IoU = intersection / hull, 0 when the hull is 0
+ *   (eval/eval_tvqa_plus.py:14-22); adds span_rows, span_right (answer == target), asa, the nine bins iou >= thd_host[k], iou_sum.
+ *   thd_host: nine HOST doubles (np.arange(0.1, 1, 0.1) as the evaluation forms them), read before the call returns and passed to
+ *   the kernel by value.  rows_out (N, 3) int32, if given, receives what stage_answer_spans would write.
+ * STAGE_ERR_SHAPE before any launch: NULL or misaligned meter, negative sizes, C / NA / Li outside the limits, a NULL required pointer. */
+size_t stage_meter_bytes(long long ring_cap);
+int stage_meter_reset(void* meter, long long ring_cap, void* stream);
+int stage_meter_update(void* meter, long long ring_cap, const float* logits, const long long* targets, int P, int C, const float* loss,
+                       const float* cls, const float* att, const float* ts, float att_w, float ts_w, const float* grad_norm,
+                       void* stream);
+int stage_train_loss_meter(const float* logits, const long long* targets, const float* att_loss, const float* t_loss,
+                           const float* scale_dev, float scale_host, float att_w, float ts_w, float* loss, float* dlogits, int P, int C,
+                           void* stream, void* meter, long long ring_cap);
+int stage_meter_spans(void* meter, const float* answer, const float* t_prob, const long long* targets, const double* gt,
+                      const double* thd_host, int N, int NA, int Li, int* rows_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

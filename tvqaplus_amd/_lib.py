@@ -195,6 +195,12 @@ SIGNATURES = {
     # clip + Adam on the packed gradient buffer (csrc/flat_adam.hip; tvqaplus_amd/optim.py): betas is a HOST array of two doubles
     "stage_flat_adam_ws_bytes": (SZ, [LL]),
     "stage_flat_adam_step": (I, [P, P, P, P, I, P, I, P, P, LL, F, P, F, F, F, P, SZ, P, P]),
+    # run meter (csrc/meter.hip; tvqaplus_amd/meter.py): per-step statistics in one device buffer; thd_host is a HOST array of nine doubles
+    "stage_meter_bytes": (SZ, [LL]),
+    "stage_meter_reset": (I, [P, LL, P]),
+    "stage_meter_update": (I, [P, LL, P, P, I, I, P, P, P, P, F, F, P, P]),
+    "stage_train_loss_meter": (I, [P, P, P, P, P, F, F, F, P, P, I, I, P, P, LL]),
+    "stage_meter_spans": (I, [P, P, P, P, P, P, I, I, I, P, P]),
 }
 
 ABI_VERSION = 5    # include/stage_hip.h: STAGE_HIP_ABI_VERSION (tests/test_abi.py holds the two together)

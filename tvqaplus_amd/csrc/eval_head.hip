@@ -5,82 +5,10 @@
 //
 // Memory safety: every index into a row is built from loop bounds below Li or from a scan / reduction result that starts at 0 and
 // is only ever replaced by the index of an element below Li (an out-of-range slot holds -inf and never wins a strict compare).
-#include "common.h"
+#include "head_shared.h"     // EVAL_MAX_LI, block_scan_max_first, block_argmax_first, answer_span_decode
 #include "../../include/stage_hip.h"
 
-#define EVAL_MAX_LI 2048     // = SPAN_MAX_LI of csrc/groups.hip
-#define EVAL_SCAN_PER 8      // EVAL_MAX_LI / 256: elements per thread of the block scan
-
 namespace {
-
-// Inclusive running maximum of n <= EVAL_MAX_LI LDS floats together with the FIRST position that attains it (a later element
-// only takes over with a strictly larger value, as torch.cummax's first-occurrence indices restricted to strict increases and
-// evaluation.find_max_pair's `lead`).  rev: the scan runs from the last element down (suffix maximum; the index is then the LAST
-// position of the maximum).  out_i may be NULL.  All 256 threads call it; v must be complete (barrier) before the call, the
-// outputs are complete (barrier) when it returns; out_v / out_i must not alias v.  shv / shi: 4 words of LDS each.
-__device__ __forceinline__ void block_scan_max_first(const float* v, float* out_v, int* out_i, int n, bool rev, float* shv,
-                                                     int* shi) {
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    float loc[EVAL_SCAN_PER];
-    float bv = -INFINITY;
-    int bi = 0;
-#pragma unroll
-    for (int u = 0; u < EVAL_SCAN_PER; u++) {
-        const int k = tid * EVAL_SCAN_PER + u;
-        const float x = k < n ? v[rev ? n - 1 - k : k] : -INFINITY;
-        loc[u] = x;
-        if (x > bv) { bv = x; bi = k; }
-    }
-    // inclusive scan of the thread aggregates inside the wave: combine(left, right) = right.v > left.v ? right : left
-    float sv = bv;
-    int si = bi;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const float pv = __shfl_up(sv, o);
-        const int pi = __shfl_up(si, o);
-        if (lane >= o && !(sv > pv)) { sv = pv; si = pi; }
-    }
-    if (lane == 63) { shv[w] = sv; shi[w] = si; }
-    const float lv = __shfl_up(sv, 1);       // aggregate of the wave's lanes before this one
-    const int li = __shfl_up(si, 1);
-    __syncthreads();
-    float ev = -INFINITY;                    // everything before this thread's first element
-    int ei = 0;
-    for (int ww = 0; ww < w; ww++)
-        if (shv[ww] > ev) { ev = shv[ww]; ei = shi[ww]; }
-    if (lane > 0 && lv > ev) { ev = lv; ei = li; }
-#pragma unroll
-    for (int u = 0; u < EVAL_SCAN_PER; u++) {
-        const int k = tid * EVAL_SCAN_PER + u;
-        if (loc[u] > ev) { ev = loc[u]; ei = k; }
-        if (k < n) {
-            const int pos = rev ? n - 1 - k : k;
-            out_v[pos] = ev;
-            if (out_i) out_i[pos] = rev ? n - 1 - ei : ei;
-        }
-    }
-    __syncthreads();
-}
-
-// (largest value, smallest index among its holders) over the workgroup; every thread returns the result.  A thread that holds
-// nothing passes (-inf, INT_MAX).  bv / bi: 256 words of LDS each.
-__device__ __forceinline__ void block_argmax_first(float& val, int& idx, float* bv, int* bi) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    bv[tid] = val;
-    bi[tid] = idx;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (tid < o) {
-            const float v2 = bv[tid + o];
-            const int i2 = bi[tid + o];
-            if (v2 > bv[tid] || (v2 == bv[tid] && i2 < bi[tid])) { bv[tid] = v2; bi[tid] = i2; }
-        }
-        __syncthreads();
-    }
-    val = bv[0];
-    idx = bi[0];
-}
 
 // Span of one candidate row r = (n, a) (model/stage.py:440-448, model/model_utils.py:92-123): softmax over the frames of the start
 // and end scores -- span_kernel's arithmetic: expf(v - max), block sum in fixed order, divide -- then the arg max of
@@ -232,40 +160,11 @@ __global__ __launch_bounds__(256) void eval_pool_kernel(const float* __restrict_
 // the specification forms it); a best product <= 0 gives (0, 1).  out (N, 3) int32 [st, ed, answer].  NaN-free input.
 __global__ __launch_bounds__(256) void answer_span_kernel(const float* __restrict__ answer, const float* __restrict__ t_prob,
                                                           int* __restrict__ out, int NA, int Li) {
-    __shared__ float ps[EVAL_MAX_LI], pe[EVAL_MAX_LI], rm[EVAL_MAX_LI], sh[4];
-    __shared__ int lead[EVAL_MAX_LI];
-    __shared__ float bv[256];
-    __shared__ int bi[256], shi[4];
-    const int tid = threadIdx.x;
+    __shared__ AnswerSpanLds L;
     const long n = blockIdx.x;
-    int pred = 0;
-    float top = -INFINITY;
-    for (int a = 0; a < NA; a++) {           // NA <= 64 words, the same for every thread: broadcast reads
-        const float v = answer[n * NA + a];
-        if (v > top) { top = v; pred = a; }
-    }
-    const float* x = t_prob + (n * NA + pred) * (long)Li * 2;
-    for (int i = tid; i < Li; i += 256) {
-        const float2 v = reinterpret_cast<const float2*>(x)[i];
-        ps[i] = v.x;
-        pe[i] = v.y;
-    }
-    __syncthreads();
-    block_scan_max_first(ps, rm, lead, Li, false, sh, shi);
-    float best = -INFINITY;
-    int ed = 0x7fffffff;
-    for (int i = tid; i < Li; i += 256) {
-        const float v = rm[i] * pe[i];
-        if (v > best) { best = v; ed = i; }
-    }
-    block_argmax_first(best, ed, bv, bi);
-    if (tid == 0) {
-        int st = 0;
-        if (ed == 0x7fffffff || !(best > 0.f)) {
-            ed = 1;
-        } else {
-            st = lead[ed];
-        }
+    int st, ed, pred;
+    answer_span_decode(answer, t_prob, n, NA, Li, L, st, ed, pred);
+    if (threadIdx.x == 0) {
         out[3 * n] = st;
         out[3 * n + 1] = ed;
         out[3 * n + 2] = pred;

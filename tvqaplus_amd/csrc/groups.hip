@@ -11,7 +11,7 @@
 //   tmp    backward-only scratch (gradients in flight, transposed weights, kernel workspaces), stage_grp_*_bwd_tmp_bytes()
 //   flags  host ints written by the forward and handed back to the backward (which optional kernel paths were taken)
 //   params / grads  host arrays of device pointers in the order each group documents; seeds: host array, one per dropout site
-#include "common.h"
+#include "head_shared.h"     // train_loss_rows / train_loss_value: shared with csrc/meter.hip
 #include "../../include/stage_hip.h"
 
 namespace {
@@ -1272,23 +1272,9 @@ __global__ __launch_bounds__(256) void train_loss_kernel(const float* __restrict
                                                          const float* __restrict__ scale_dev, float scale_host, float att_w, float ts_w,
                                                          float* __restrict__ loss, float* __restrict__ dlogits, int P, int C) {
     __shared__ float sh[4];
-    const int tid = threadIdx.x;
     const float scale = scale_dev ? scale_dev[0] : scale_host;
-    float ce = 0.f;
-    for (int r = tid; r < P; r += 256) {
-        const float* x = logits + (long)r * C;
-        float m = -INFINITY;
-        for (int c = 0; c < C; c++) m = fmaxf(m, x[c]);
-        float sum = 0.f;
-        for (int c = 0; c < C; c++) sum += expf(x[c] - m);
-        const float lse = m + logf(sum);
-        const long long t = targets[r];
-        const bool ign = t < 0;
-        for (int c = 0; c < C; c++) dlogits[(long)r * C + c] = ign ? 0.f : scale * (expf(x[c] - lse) - (c == (int)t ? 1.f : 0.f));
-        ce += ign ? 0.f : (t < C ? lse - x[(int)t] : NAN);
-    }
-    ce = block_sum256(ce, sh);
-    if (tid == 0) loss[0] = ce * scale + (att_loss ? att_w * att_loss[0] : 0.f) + (t_loss ? ts_w * t_loss[0] : 0.f);
+    const float ce = train_loss_rows(logits, targets, scale, dlogits, P, C, sh);
+    if (threadIdx.x == 0) loss[0] = train_loss_value(ce, scale, att_loss, t_loss, att_w, ts_w);
 }
 extern "C" int stage_train_loss(const float* logits, const long long* targets, const float* att_loss, const float* t_loss,
                                 const float* scale_dev, float scale_host, float att_w, float ts_w, float* loss, float* dlogits, int P, int C,

@@ -151,7 +151,8 @@ class _ConvLinearParams(nn.Module):
 # ---------------------------------------------------------------------------------------------------------------
 # the model
 # ---------------------------------------------------------------------------------------------------------------
-def reference_loss(outputs, targets, att_loss, temporal_loss, n_examples: int, att_weight: float = 0.1, ts_weight: float = 0.5, scale=None):
+def reference_loss(outputs, targets, att_loss, temporal_loss, n_examples: int, att_weight: float = 0.1, ts_weight: float = 0.5, scale=None,
+                   meter=None):
     """The training loss of the reference's driver (main.py:55-60) for the outputs of ``STAGE.forward`` in training mode:
 
         criterion(outputs, targets) * (len(qids) / len(targets)) + att_weight * att_loss + ts_weight * temporal_loss
@@ -161,9 +162,13 @@ def reference_loss(outputs, targets, att_loss, temporal_loss, n_examples: int, a
     of WHERE they sit: right behind the proposal read-back of ``get_proposals``, the one point of the step where the device has nothing
     queued and waits for the host call by call (profiles/r06_step_idle_gaps.txt).  A drop-in for those four lines of a training loop,
     optional: the eager lines give the same value (tests/test_hip_groups.py::test_reference_loss_matches_the_eager_lines).
-    ``scale``: overrides len(qids) / len(targets) (multi-GPU: ``parallel.global_loss_scale(..., as_tensor=True)``)."""
+    ``scale``: overrides len(qids) / len(targets) (multi-GPU: ``parallel.global_loss_scale(..., as_tensor=True)``).
+    ``meter``: a ``tvqaplus_amd.meter.RunMeter``; the same launch then also does the bookkeeping of main.py:69-74 (loss, cls / att / ts
+    parts, predictions against targets) in the meter's device buffer -- same loss, same gradient, no read-back."""
     if scale is None:
         scale = float(n_examples) / len(targets)
+    if meter is not None:
+        return groups.train_loss(outputs, targets, att_loss, temporal_loss, scale, att_weight, ts_weight, meter=meter)
     return groups.train_loss(outputs, targets, att_loss, temporal_loss, scale, att_weight, ts_weight)
 
 
