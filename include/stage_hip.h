@@ -428,6 +428,23 @@ int stage_tscores_bwd(const float* dout, const float* tm, float* d_st, float* d_
  * the proposal bookkeeping needs).  Li <= 2048.                                                                               */
 int stage_gt_spans(const float* t_scores, const long long* target, const long long* lab_st, const long long* lab_ed,
                    float* spans, int N, int NA, int Li, void* stream);
+/* Top-K span proposals (csrc/topk_spans.hip; model/model_utils.py:92-123 find_max_triples with topN = K, model/stage.py:389-438
+ * get_proposals(max_num_proposal = K)): the K pairs (st <= ed) of a row with the largest p_st[st] * p_ed[ed], value descending, equal
+ * values by ascending st * Li + ed (a total order: the list is unique).  One workgroup per row, O(Li) memory, no (Li, Li) product.
+ * Ranks that no pair fills (Li (Li + 1) / 2 < K) are st = ed = -1, confidence 0.  The softmax and the product are stage_gt_spans'
+ * arithmetic, so rank 0 carries the bits stage_gt_spans / stage_grp_eval_head_fwd report.
+ * stage_topk_spans_supported: 1 <= Li <= 2048 and 1 <= K <= STAGE_TOPK_MAX (needs no GPU); elsewhere the other two return
+ *   STAGE_ERR_SHAPE before a launch.
+ * stage_gt_spans_topk: stage_gt_spans with K ranks.  spans (3K + 3, N) float: rows 3k, 3k + 1, 3k + 2 = start, end, confidence of
+ *   rank k, then label start, label end, answer index; K = 1 writes exactly the (6, N) of stage_gt_spans.
+ * stage_topk_spans: x (R, Li, 2) [start, end] per frame, 8-byte aligned; is_prob == 0: scores, softmaxed over the frames here (as
+ *   the evaluation head reads them); is_prob != 0: probabilities >= 0, used as given (as stage_answer_spans reads them).
+ *   span (R, K, 2) int32 [st, ed], conf (R, K).                                                                                  */
+#define STAGE_TOPK_MAX 8
+int stage_topk_spans_supported(int Li, int K);
+int stage_gt_spans_topk(const float* t_scores, const long long* target, const long long* lab_st, const long long* lab_ed,
+                        float* spans, int N, int NA, int Li, int K, void* stream);
+int stage_topk_spans(const float* x, int is_prob, int* span, float* conf, long long R, int Li, int K, void* stream);
 /* temporal loss (model/stage.py:539-555) and d loss / d t_scores in one pass; scratch: N floats; cand_offset: global index of
  * local candidate 0 (candidate-sharded batches: examples whose ground truth is not local contribute nothing); na_total: the
  * model's candidate count over all ranks (a target outside [0, na_total) makes the loss NaN; <= 0: cand_offset + NA)        */
@@ -463,7 +480,7 @@ int stage_att_hard_negatives(const float* scores, const long long* row_off, cons
                              long long* flat_neg, void* stream);
 /* G6 proposal pooling + answer classifier (model/stage.py:420-467, 526-536): first (N*NA, Li, D), mask (N*NA, Li), glob / idx_g =
  * stage_masked_max_fwd(first, mask) computed ahead; meta (device int32) = src[P] | win[2P] | inv[2N] (proposal -> example, frame
- * window [st, ed), example -> its <= 2 proposals or -1).  logits (P*NA).  params / grads: ln_g ln_b W c (2D wide); seeds[1].
+ * window [st, ed), example -> its <= 2 proposals or -1; more per example: stage_grp_pool_cls_bwd_s).  logits (P*NA).  params / grads: ln_g ln_b W c (2D wide); seeds[1].
  * d_first (N*NA, Li, D) receives both pooling paths.                                                                          */
 size_t stage_grp_pool_cls_arena_bytes(long long P, int NA, int D);
 int stage_grp_pool_cls_fwd(const float* first, const float* mask, const float* glob, const int* meta, const float* const* params,
@@ -473,6 +490,14 @@ size_t stage_grp_pool_cls_bwd_tmp_bytes(long long P, int NA, int D);
 int stage_grp_pool_cls_bwd(const float* d_logits, const float* mask, const int* idx_g, const int* meta, const float* const* params,
                            float* const* grads, float* d_first, const void* arena, size_t arena_bytes, void* tmp, size_t tmp_bytes,
                            int N, int NA, int Li, int D, long long P, float p_drop, const unsigned long long* seeds, void* stream);
+/* The same backward with up to `slots` proposals per example (max_num_proposal = slots - 1 predicted spans + the label's):
+ * meta = src[P] | win[2P] | inv[slots * N], inv (N, slots) = the example's proposals in ascending slot order or -1; the sums over
+ * an example's proposals run in that order.  1 <= slots <= STAGE_TOPK_MAX + 1 (STAGE_ERR_SHAPE otherwise).  The forward reads src
+ * and win only and needs no counterpart; stage_grp_pool_cls_bwd is this call with slots = 2.                                     */
+int stage_grp_pool_cls_bwd_s(const float* d_logits, const float* mask, const int* idx_g, const int* meta, const float* const* params,
+                             float* const* grads, float* d_first, const void* arena, size_t arena_bytes, void* tmp, size_t tmp_bytes,
+                             int N, int NA, int Li, int D, long long P, int slots, float p_drop, const unsigned long long* seeds,
+                             void* stream);
 
 /* G7 evaluation head (model/stage.py:440-448, 526-536 outside training; csrc/eval_head.hip): what get_proposals + the classifier do in
  * eval()/inference for R = N * NA independent rows, forward only.  first (R, Li, D), mask (R, Li), t_scores (R, Li, 2).

@@ -130,6 +130,10 @@ SIGNATURES = {
     "stage_tscores_fwd": (I, [P, P, P, P, I, I, I, P]),
     "stage_tscores_bwd": (I, [P, P, P, P, I, I, I, P]),
     "stage_gt_spans": (I, [P, P, P, P, P, I, I, I, P]),
+    # top-K span proposals (csrc/topk_spans.hip): max_num_proposal > 1 in training, n-best decoding of a score row
+    "stage_topk_spans_supported": (I, [I, I]),
+    "stage_gt_spans_topk": (I, [P, P, P, P, P, I, I, I, I, P]),
+    "stage_topk_spans": (I, [P, I, P, P, LL, I, I, P]),
     "stage_ts_loss": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
     "stage_train_loss": (I, [P, P, P, P, P, F, F, F, P, P, I, I, P]),
     "stage_att_loss_fwd": (I, [P, P, LL, I, F, F, P, P, P]),
@@ -142,6 +146,7 @@ SIGNATURES = {
     "stage_grp_pool_cls_fwd": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, LL, F, P, P]),
     "stage_grp_pool_cls_bwd_tmp_bytes": (SZ, [LL, I, I]),
     "stage_grp_pool_cls_bwd": (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, F, P, P]),
+    "stage_grp_pool_cls_bwd_s": (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, I, F, P, P]),
     # evaluation head (csrc/eval_head.hip; G7 in csrc/groups.hip) and the prediction writer's span decoder
     "stage_eval_head_supported": (I, [I, I, I]),
     "stage_grp_eval_head_arena_bytes": (SZ, [LL, I, I]),
@@ -241,6 +246,8 @@ def load() -> ctypes.CDLL:
 
 
 STAGE_DT_F16, STAGE_DT_BF16 = 1, 2     # include/stage_hip.h: dtype codes of the half-precision feature entry points
+
+STAGE_TOPK_MAX = 8        # include/stage_hip.h: the largest K of the top-K span kernels (max_num_proposal, n_best)
 
 STAGE_ERR_SHAPE = -1      # include/stage_hip.h
 STAGE_ERR_WORKSPACE = -2

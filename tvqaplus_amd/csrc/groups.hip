@@ -1096,11 +1096,15 @@ __global__ __launch_bounds__(256) void pool_fwd_kernel(const float* __restrict__
     }
 }
 // dx[source row, l, d] = m[l] * ( sum_j [idx[r_j, d] == l] dpooled[r_j, d]  +  [idx_g[d] == l] sum_j dpooled[r_j, D + d] ),
-// r_j = the (at most two) proposals of the example: inv (N, 2), -1 = none.  The whole dx is written.
+// r_j = the proposals of the example in ascending slot order (the order of the sums): inv (N, slots), -1 = none.  SLOTS = 2: the
+// label's span + at most one predicted span, unrolled; SLOTS = 0: `slots` <= STAGE_TOPK_MAX + 1 at run time (max_num_proposal > 1).
+// The whole dx is written.
+template <int SLOTS>
 __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__ dpooled, const int* __restrict__ idx,
                                                        const int* __restrict__ idx_g, const float* __restrict__ m,
                                                        const int* __restrict__ inv, float* __restrict__ dx, long Rs, int NA, int L,
-                                                       int D4) {
+                                                       int D4, int slots) {
+    const int ns = SLOTS ? SLOTS : slots;
     const long total = Rs * L * D4;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int q = (int)(e % D4);
@@ -1111,8 +1115,8 @@ __global__ __launch_bounds__(256) void pool_bwd_kernel(const float* __restrict__
         const int a = (int)(sr % NA);
         float4 o = make_float4(0.f, 0.f, 0.f, 0.f), gg = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int p = inv[2 * n + j];
+        for (int j = 0; j < ns; j++) {
+            const int p = inv[ns * n + j];
             if (p < 0) continue;
             const long r = (long)p * NA + a;
             const int4 bi = *reinterpret_cast<const int4*>(idx + (r * D4 + q) * 4);
@@ -1264,7 +1268,7 @@ extern "C" int stage_ts_loss(const float* t_scores, const long long* target, con
 // The caller's loss line (main.py:55-60): loss = CE_sum(logits, targets) * scale + att_w * att_loss + ts_w * t_loss, and the gradient
 // of the cross entropy w.r.t. the logits (scale * (softmax - onehot)) in the same pass -- one launch instead of the ~20 tiny ones of
 // the eager expression and its backward, which arrive one host call at a time right behind the step's only read-back, while the
-// device has nothing else queued (profiles/r06_step_idle_gaps.txt).  One workgroup: P = proposals (<= 2 N), C = candidates.
+// device has nothing else queued (profiles/r06_step_idle_gaps.txt).  One workgroup: P = proposals (any number: <= (max_num_proposal + 1) N), C = candidates.
 // scale: scale_dev[0] if given (multi-GPU: the global N / N_new as a device word), else scale_host.  A target outside [0, C) is
 // ignored like F.cross_entropy's ignore_index (-100) when negative, NaN otherwise (the eager call raises).
 __global__ __launch_bounds__(256) void train_loss_kernel(const float* __restrict__ logits, const long long* __restrict__ targets,
@@ -1304,7 +1308,8 @@ extern "C" int stage_att_loss_bwd(const long long* flat, const float* coef, cons
 
 // ---- G6  proposal pooling + answer classifier (model/stage.py:420-467, 526-536; LinearWrapper :15-32) -----------------------
 //     first (N*NA, Li, D), mask (N*NA, Li), glob / idx_g = its global masked max (stage_masked_max_fwd, computed before the
-//     proposal read-back), meta (int32, device): src[P] | win[2P] | inv[2N].  logits (P*NA).  params: ln_g ln_b W c (2D wide);
+//     proposal read-back), meta (int32, device): src[P] | win[2P] | inv[slots*N] | tgt[P] (slots = 2 unless ..._bwd_s says otherwise;
+//     tgt is the caller's).  logits (P*NA).  params: ln_g ln_b W c (2D wide);
 //     seeds[1]; no flags.  Backward: d_first (N*NA, Li, D) receives BOTH pooling paths (local windows and the global max).
 namespace {
 struct PcArena { float *pooled, *y, *mean, *rstd; int* idx; size_t bytes; };
@@ -1353,10 +1358,11 @@ extern "C" int stage_grp_pool_cls_fwd(const float* first, const float* mask, con
     return lin_fwd(a.y, P[2], P[3], logits, nullptr, &none, Rn, 1, 2 * D, 0, st);
 }
 
-extern "C" int stage_grp_pool_cls_bwd(const float* d_logits, const float* mask, const int* idx_g, const int* meta,
-                                      const float* const* P, float* const* G, float* d_first, const void* arena, size_t arena_bytes,
-                                      void* tmp, size_t tmp_bytes, int N, int NA, int Li, int D, long long Pn, float p,
-                                      const unsigned long long* seeds, void* st) {
+extern "C" int stage_grp_pool_cls_bwd_s(const float* d_logits, const float* mask, const int* idx_g, const int* meta,
+                                        const float* const* P, float* const* G, float* d_first, const void* arena, size_t arena_bytes,
+                                        void* tmp, size_t tmp_bytes, int N, int NA, int Li, int D, long long Pn, int slots, float p,
+                                        const unsigned long long* seeds, void* st) {
+    if (slots < 1 || slots > STAGE_TOPK_MAX + 1) return STAGE_ERR_SHAPE;
     const long Rn = (long)Pn * NA;
     PcArena a = pc_layout((void*)arena, Rn, D);
     PcTmp t = pc_tmp(tmp, Rn, D);
@@ -1366,10 +1372,22 @@ extern "C" int stage_grp_pool_cls_bwd(const float* d_logits, const float* mask, 
                             stage_ln_bwd_ws_bytes(2 * D), st));
     const int* inv = meta + 3 * Pn;
     const long Rs = (long)N * NA;
-    hipLaunchKernelGGL(pool_bwd_kernel, dim3(capped_grid(Rs * Li * (D / 4), 256)), dim3(256), 0, (hipStream_t)st, t.dpooled, a.idx, idx_g,
-                       mask, inv, d_first, Rs, NA, Li, D / 4);
+    const dim3 grid(capped_grid(Rs * Li * (D / 4), 256));
+    if (slots == 2)
+        hipLaunchKernelGGL(pool_bwd_kernel<2>, grid, dim3(256), 0, (hipStream_t)st, t.dpooled, a.idx, idx_g, mask, inv, d_first, Rs, NA, Li,
+                           D / 4, 2);
+    else
+        hipLaunchKernelGGL(pool_bwd_kernel<0>, grid, dim3(256), 0, (hipStream_t)st, t.dpooled, a.idx, idx_g, mask, inv, d_first, Rs, NA, Li,
+                           D / 4, slots);
     STAGE_LAUNCH_CHECK();
     return 0;
+}
+extern "C" int stage_grp_pool_cls_bwd(const float* d_logits, const float* mask, const int* idx_g, const int* meta,
+                                      const float* const* P, float* const* G, float* d_first, const void* arena, size_t arena_bytes,
+                                      void* tmp, size_t tmp_bytes, int N, int NA, int Li, int D, long long Pn, float p,
+                                      const unsigned long long* seeds, void* st) {
+    return stage_grp_pool_cls_bwd_s(d_logits, mask, idx_g, meta, P, G, d_first, arena, arena_bytes, tmp, tmp_bytes, N, NA, Li, D, Pn, 2, p,
+                                    seeds, st);
 }
 
 // ---- G7  evaluation head: span of every candidate row + windowed / global pooling + answer classifier (model/stage.py:440-448,

@@ -6,6 +6,7 @@ The reference splits this over ``inference.py`` (span decoding ``find_max_pair``
 
 * ``find_max_pair_batch``   -- the span decoder for a whole batch ON THE DEVICE (no ``.cpu()`` per question); the
                                host version ``find_max_pair`` is kept as the specification it is tested against
+* ``find_max_triples_batch`` -- the n best spans of a row (model/model_utils.py:92-123 for a batch), on the device in O(L) memory
 * ``PredictionWriter``      -- accumulates ``{"ts_answer": {qid: [[st, ed], answer]}, "raw_bbox": [...]}`` from the
                                model's ``inference_mode`` outputs with the reference's time mapping, and saves it
 * ``compute_temporal_metrics``, ``detection_map`` (PASCAL-VOC AP as maskrcnn-benchmark's voc evaluation, numpy),
@@ -63,6 +64,50 @@ def find_max_pair_batch(p_st: torch.Tensor, p_ed: torch.Tensor) -> Tuple[torch.T
     return st, ed, val
 
 
+def _find_max_triples_host(p_st: torch.Tensor, p_ed: torch.Tensor, top_n: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The specification of the top-K span search, as plain torch: every pair (st <= ed) valued p_st[st] * p_ed[ed] (one
+    multiplication in the tensors' type), sorted by value descending with equal values in ascending st * L + ed (a stable sort of the
+    row-major product), the first top_n taken; ranks past the L (L + 1) / 2 pairs are (-1, -1) with value 0."""
+    R, L = p_st.shape
+    span = torch.full((R, top_n, 2), -1, dtype=torch.int64, device=p_st.device)
+    conf = torch.zeros((R, top_n), dtype=p_st.dtype, device=p_st.device)
+    upper = torch.ones(L, L, dtype=torch.bool, device=p_st.device).triu().view(-1)
+    n = min(top_n, L * (L + 1) // 2)
+    for r in range(R):                                   # one (L, L) product at a time
+        prod = (p_st[r].unsqueeze(1) * p_ed[r].unsqueeze(0)).reshape(-1)
+        val, flat = torch.sort(prod[upper], descending=True, stable=True)
+        flat = torch.nonzero(upper).view(-1)[flat[:n]]
+        span[r, :n, 0], span[r, :n, 1] = flat // L, flat % L
+        conf[r, :n] = val[:n]
+    return span, conf
+
+
+def find_max_triples_batch(p_st: torch.Tensor, p_ed: torch.Tensor, top_n: int, prob_thd: Optional[float] = None
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """model/model_utils.py:92-123 (find_max_triples) for R rows, wherever the tensors live: the top_n pairs (st <= ed) with the
+    largest p_st[st] * p_ed[ed].  p_st, p_ed: (R, L) probabilities -> (span (R, top_n, 2) int64 [st, ed], conf (R, top_n)).
+    Order: value descending, equal values by ascending st * L + ed (``STAGE._best_span``'s rule; the reference's argsort leaves
+    ties to numpy's unstable sort).  Ranks without a pair -- where the reference lists a zero of the lower triangle -- and, with
+    ``prob_thd``, ranks whose value is below it (a suffix of the list) are (-1, -1) with value 0.
+    fp32 rows on the GPU go through one kernel (``groups.topk_spans``, O(L) memory per row); anything else, and shapes the kernel
+    declines (L > 2048, top_n > 8), through ``_find_max_triples_host``, which is also the kernel's specification."""
+    if p_st.dim() != 2 or p_st.shape != p_ed.shape or top_n < 1:
+        raise ValueError("find_max_triples_batch: p_st, p_ed must be (R, L) and top_n >= 1")
+    span = conf = None
+    if p_st.is_cuda and p_ed.is_cuda and p_st.dtype == torch.float32 and p_ed.dtype == torch.float32 and p_st.shape[0] >= 1:
+        from . import groups
+        if groups.topk_spans_supported(p_st.shape[1], top_n):
+            span, conf = groups.topk_spans(torch.stack([p_st.detach(), p_ed.detach()], dim=2), top_n, is_prob=True)
+            span = span.long()
+    if span is None:
+        span, conf = _find_max_triples_host(p_st.detach(), p_ed.detach(), top_n)
+    if prob_thd is not None:
+        drop = (conf < prob_thd) | (span[:, :, 0] < 0)
+        span = torch.where(drop.unsqueeze(2), torch.full_like(span, -1), span)
+        conf = torch.where(drop, torch.zeros_like(conf), conf)
+    return span, conf
+
+
 def _device_rows(answer: torch.Tensor, t_scores: torch.Tensor) -> Optional[torch.Tensor]:
     """(N, 3) [st, ed, answer] from ONE kernel (``groups.answer_spans``: the decoder above, same tie rules) when both tensors are
     fp32 on the GPU and the kernel takes the shape; None otherwise (the torch composition of ``find_max_pair_batch`` then runs)."""
@@ -81,8 +126,16 @@ class PredictionWriter:
     softmaxed temporal scores and mapped to seconds (frames are sampled at 0.5 fps: ``st * 2 + offset``,
     ``(ed + 1) * 2 + offset`` with ``offset = (image_indices[0] % 6) / 3``), plus the raw box predictions."""
 
-    def __init__(self):
+    def __init__(self, n_best: int = 1):
+        """``n_best`` > 1: the file gains ``"ts_nbest": {qid: [[st_sec, ed_sec, conf], ...]}``, the n_best spans of the predicted
+        answer by ``find_max_triples_batch`` (best first, same time mapping, fewer entries when the row has fewer pairs).  The
+        ``ts_answer`` records keep their layout, so the evaluation reads such a file unchanged; n_best = 1 writes today's file."""
+        if int(n_best) < 1:
+            raise ValueError("PredictionWriter: n_best must be >= 1")
+        self.n_best = int(n_best)
         self.predictions: Dict[str, object] = dict(ts_answer={}, raw_bbox=[])
+        if self.n_best > 1:
+            self.predictions["ts_nbest"] = {}
 
     def add_batch(self, outputs: Mapping[str, object], qids: Sequence[int], image_indices: Sequence[Sequence[int]]) -> None:
         answer, t_scores = outputs["answer"], outputs["t_scores"]             # (N, 5), (N, 5, Li, 2) softmaxed over Li
@@ -93,12 +146,23 @@ class PredictionWriter:
             picked = t_scores.detach().gather(1, pred.view(N, 1, 1, 1).expand(N, 1, Li, 2)).squeeze(1)    # (N, Li, 2)
             st, ed, _ = find_max_pair_batch(picked[:, :, 0], picked[:, :, 1])
             rows = torch.stack([st, ed, pred], dim=1)
+        nbest = None
+        if self.n_best > 1:
+            N, _, Li, _ = t_scores.shape
+            picked = t_scores.detach().gather(1, rows[:, 2].long().view(N, 1, 1, 1).expand(N, 1, Li, 2)).squeeze(1)      # (N, Li, 2)
+            span, conf = find_max_triples_batch(picked[:, :, 0], picked[:, :, 1], self.n_best)
+            nbest = torch.cat([span.double(), conf.double().unsqueeze(2)], dim=2).cpu().tolist()    # one more copy per batch
         rows = rows.cpu().tolist()                                             # ONE copy per batch
         if outputs.get("att_predictions"):
             self.predictions["raw_bbox"] += outputs["att_predictions"]
         for qid, (s, e, a), img in zip(qids, rows, image_indices):
             offset = (img[0] % 6) / 3
             self.predictions["ts_answer"][str(qid)] = [[s * 2 + offset, (e + 1) * 2 + offset], int(a)]
+        if nbest is not None:
+            for qid, ranks, img in zip(qids, nbest, image_indices):
+                offset = (img[0] % 6) / 3
+                self.predictions["ts_nbest"][str(qid)] = [[int(s) * 2 + offset, (int(e) + 1) * 2 + offset, c]
+                                                          for (s, e, c) in ranks if s >= 0]
 
     def save(self, path: str) -> None:
         with open(path, "w") as f:

@@ -657,6 +657,47 @@ def gt_spans(t_scores, target, lab_st, lab_ed):
     return spans
 
 
+def topk_spans_supported(Li: int, k: int) -> bool:
+    """The top-K span kernels (csrc/topk_spans.hip) take 1 <= Li <= 2048 and 1 <= k <= 8 (answers without a GPU)."""
+    return bool(_lib.load().stage_topk_spans_supported(int(Li), int(k)))
+
+
+def gt_spans_topk(t_scores, target, lab_st, lab_ed, k: int):
+    """``gt_spans`` with the k best spans of the ground-truth candidate (model/stage.py:408-418 with max_num_proposal = k;
+    model/model_utils.py:92-123): (3k + 3, N) device floats -- rows 3j, 3j + 1, 3j + 2 = start, end, confidence of rank j (value
+    descending, ties by ascending start * Li + end; a rank no pair fills is -1, -1, 0), then the label's start, end and the answer
+    index.  k = 1 gives the bytes of ``gt_spans``."""
+    t = _chk(t_scores.detach(), "t_scores")
+    N, NA, Li, _ = t.shape
+    if not topk_spans_supported(Li, k):
+        raise Unsupported("stage_gt_spans_topk: Li = %d, K = %d" % (Li, k))
+    target, lab_st, lab_ed = (_chk(v, "labels", torch.int64) for v in (target, lab_st, lab_ed))
+    spans = torch.empty(3 * k + 3, N, dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        _rc(_lib.load().stage_gt_spans_topk(t.data_ptr(), target.data_ptr(), lab_st.data_ptr(), lab_ed.data_ptr(), spans.data_ptr(), N, NA,
+                                            Li, int(k), _stream()), "stage_gt_spans_topk")
+    return spans
+
+
+def topk_spans(x, k: int, is_prob: bool = False):
+    """The k best spans of R rows in O(Li) memory per row: x (R, Li, 2) [start, end] per frame -> span (R, k, 2) int32 [st, ed] with
+    st <= ed, conf (R, k) = p_st[st] * p_ed[ed], value descending, ties by ascending st * Li + ed; ranks no pair fills (Li (Li + 1) / 2
+    < k) are -1, -1 with confidence 0.  ``is_prob`` false: x holds scores, softmaxed over the frames in the kernel (the evaluation
+    head's reading); true: probabilities, used as given (the prediction writer's reading).  No autograd node."""
+    x = _chk(x.detach(), "x")
+    if x.dim() != 3 or x.shape[2] != 2:
+        raise ValueError("topk_spans: x must be (R, Li, 2)")
+    R, Li, _ = x.shape
+    if not topk_spans_supported(Li, k):
+        raise Unsupported("stage_topk_spans: Li = %d, K = %d" % (Li, k))
+    span = torch.empty(R, k, 2, dtype=torch.int32, device=x.device)
+    conf = torch.empty(R, k, dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _rc(_lib.load().stage_topk_spans(x.data_ptr(), int(bool(is_prob)), span.data_ptr(), conf.data_ptr(), R, Li, int(k), _stream()),
+            "stage_topk_spans")
+    return span, conf
+
+
 def masked_max_raw(x, mask):
     """(R, L, D), (R, L) -> max (R, D), argmax (R, D) int32; no autograd node (the pooling group owns this gradient)."""
     x, mask = _chk(x.detach(), "x"), _chk(mask, "mask")
@@ -675,7 +716,7 @@ class _PoolCls(torch.autograd.Function):
         first, mask, glob = _chk(first, "first"), _chk(mask, "mask"), _chk(glob, "glob")
         idx_g, meta = _chk(idx_g, "idx_g", torch.int32), _chk(meta, "meta", torch.int32)
         params = _params(params)
-        N, NA, Li, D, P = dims
+        N, NA, Li, D, P = dims[:5]
         lib = _lib.load()
         ab = _size("stage_grp_pool_cls_arena_bytes", P, NA, D)
         arena = _buf(ab, first.device)
@@ -683,29 +724,40 @@ class _PoolCls(torch.autograd.Function):
         _rc(lib.stage_grp_pool_cls_fwd(first.data_ptr(), mask.data_ptr(), glob.data_ptr(), meta.data_ptr(), _ptrs(params), logits.data_ptr(),
                                        arena.data_ptr(), ab, N, NA, Li, D, P, float(p), _u64(seeds), _stream()), "stage_grp_pool_cls_fwd")
         ctx.save_for_backward(first, mask, idx_g, meta, arena, *params)
-        ctx.cfg = (dims, float(p), tuple(seeds), ab)
+        ctx.cfg = ((N, NA, Li, D, P, int(dims[5]) if len(dims) > 5 else 2), float(p), tuple(seeds), ab)
         return logits
 
     @_on_device
     def backward(ctx, d_logits):
         first, mask, idx_g, meta, arena, *params = ctx.saved_tensors
-        (N, NA, Li, D, P), p, seeds, ab = ctx.cfg
+        (N, NA, Li, D, P, slots), p, seeds, ab = ctx.cfg
         d_logits = _chk(d_logits, "d_logits")
         lib = _lib.load()
         grads = _grad_views(params)
         d_first = torch.empty_like(first)
         tb = _size("stage_grp_pool_cls_bwd_tmp_bytes", P, NA, D)
         tmp = _buf(tb, first.device)
-        _rc(lib.stage_grp_pool_cls_bwd(d_logits.data_ptr(), mask.data_ptr(), idx_g.data_ptr(), meta.data_ptr(), _ptrs(params), _ptrs(grads),
-                                       d_first.data_ptr(), arena.data_ptr(), ab, tmp.data_ptr(), tb, N, NA, Li, D, P, p, _u64(seeds),
-                                       _stream()), "stage_grp_pool_cls_bwd")
+        if slots == 2:
+            _rc(lib.stage_grp_pool_cls_bwd(d_logits.data_ptr(), mask.data_ptr(), idx_g.data_ptr(), meta.data_ptr(), _ptrs(params),
+                                           _ptrs(grads), d_first.data_ptr(), arena.data_ptr(), ab, tmp.data_ptr(), tb, N, NA, Li, D, P, p,
+                                           _u64(seeds), _stream()), "stage_grp_pool_cls_bwd")
+        else:
+            _rc(lib.stage_grp_pool_cls_bwd_s(d_logits.data_ptr(), mask.data_ptr(), idx_g.data_ptr(), meta.data_ptr(), _ptrs(params),
+                                             _ptrs(grads), d_first.data_ptr(), arena.data_ptr(), ab, tmp.data_ptr(), tb, N, NA, Li, D, P,
+                                             slots, p, _u64(seeds), _stream()), "stage_grp_pool_cls_bwd_s")
         return (d_first, None, None, None, None, None, None, None) + tuple(grads)
 
 
-def pool_classifier(first, mask, glob, idx_g, meta, dims, p: float, seeds, params):
+def pool_classifier(first, mask, glob, idx_g, meta, dims, p: float, seeds, params, slots: int = 2):
     """first (N*NA, Li, D) -> logits (P*NA, 1): local window max + global max of every proposal, LayerNorm(2D) + dropout,
-    Linear(2D -> 1).  meta (device int32): src[P] | win[2P] | inv[2N].  params: ln.w ln.b fc.w fc.b."""
-    return _PoolCls.apply(first, mask, glob, idx_g, meta, tuple(dims), p, tuple(seeds), *params)
+    Linear(2D -> 1).  dims = (N, NA, Li, D, P).  meta (device int32): src[P] | win[2P] | inv[slots * N] | tgt[P] (tgt is the
+    caller's; the kernels stop reading after inv); inv (N, slots) = the proposals of an example in ascending slot order, -1 = none.
+    ``slots``: 2 (the label's span + one predicted span), up to 9 with max_num_proposal > 1.  params: ln.w ln.b fc.w fc.b."""
+    slots = int(slots)
+    if not 1 <= slots <= _lib.STAGE_TOPK_MAX + 1:
+        raise Unsupported("pool_classifier: slots = %d" % slots)
+    dims = tuple(dims)[:5]
+    return _PoolCls.apply(first, mask, glob, idx_g, meta, dims if slots == 2 else dims + (slots,), p, tuple(seeds), *params)
 
 
 class _TsLoss(torch.autograd.Function):

@@ -172,6 +172,62 @@ def reference_loss(outputs, targets, att_loss, temporal_loss, n_examples: int, a
     return groups.train_loss(outputs, targets, att_loss, temporal_loss, scale, att_weight, ts_weight)
 
 
+def proposal_rows(host, N: int, k: int = 1, iou_thd: float = 0.5, ce_prob_thd: float = 0.01, extra_span_length: int = 3):
+    """The host half of get_proposals in training (model/stage.py:411-438; model/model_utils.py:37-89): which spans of every example
+    train the classifier.  ``host``: the read-back of ``groups.gt_spans`` / ``groups.gt_spans_topk`` as rows of Python floats -- rows
+    3j, 3j + 1, 3j + 2 = start, end (inclusive), confidence of rank j < k, then the label's start, end (inclusive) and, if present,
+    the answer index.  Per example, in order: the label's span, then the ranks with confidence >= ce_prob_thd whose IoU with the
+    label's span (intersection / hull, end exclusive) is >= iou_thd; ranks the kernel left empty (start < 0) are skipped.  Returns
+
+        src  (P)             the example of every proposal (proposals of an example are contiguous)
+        wins (2 P)           frame window [max(0, st - extra), ed + 1 + extra) of every proposal
+        inv  (N * (k + 1))   the proposals of example n in slot order at inv[(k + 1) n : (k + 1) (n + 1)], -1 = none
+        tgt  (P)             the answer index of the proposal's example ([] when ``host`` has no such row)
+
+    Pure Python on plain lists: no tensor, no device."""
+    slots = k + 1
+    lab = 3 * k
+    src, wins, inv = [], [], [-1] * (slots * N)
+    for n in range(N):
+        gs, ge = int(host[lab][n]), int(host[lab + 1][n]) + 1
+        cand = [(gs, ge)]
+        for j in range(k):
+            if host[3 * j + 2][n] >= ce_prob_thd and host[3 * j][n] >= 0:
+                ps, pe = int(host[3 * j][n]), int(host[3 * j + 1][n]) + 1
+                inter = max(0, min(pe, ge) - max(ps, gs))
+                union = max(pe, ge) - min(ps, gs)
+                if union != 0 and inter / union >= iou_thd:
+                    cand.append((ps, pe))
+        for j, (s0, e0) in enumerate(cand):
+            inv[slots * n + j] = len(src)
+            src.append(n)
+            wins += [max(0, s0 - extra_span_length), e0 + extra_span_length]
+    tgt = [int(host[lab + 2][n]) for n in src] if len(host) > lab + 2 else []
+    return src, wins, inv, tgt
+
+
+class _GatherExamples(torch.autograd.Function):
+    """``x.index_select(0, src)`` for the proposal rows of get_proposals with a backward that sums in a FIXED order: the gradient of
+    example n is the sum over its proposals inv[n, 0], inv[n, 1], ... in slot order.  index_select's own backward is an atomic
+    index_add, whose result depends on the arrival order as soon as an example has more than two proposals (max_num_proposal > 1)."""
+
+    @staticmethod
+    def forward(ctx, x, src, inv):
+        ctx.save_for_backward(inv)
+        return x.index_select(0, src)
+
+    @staticmethod
+    def backward(ctx, g):
+        (inv,) = ctx.saved_tensors                       # (N, slots) int64, -1 = none
+        shape = (inv.shape[0],) + (1,) * (g.dim() - 1)
+        out = None
+        for j in range(inv.shape[1]):
+            col = inv[:, j]
+            term = g.index_select(0, col.clamp(min=0)) * (col >= 0).to(g.dtype).view(shape)
+            out = term if out is None else out + term
+        return out, None, None
+
+
 def _block_params(blk):
     """[ln.w, ln.b, dw.w, dw.b, pw.w, pw.b] per conv layer + the final LayerNorm's pair of an encoder block, in the order the encoder
     K-groups take them.  Cached on the block (plain attribute): the Parameter OBJECTS never change (``.to()`` / the optimizer update them
@@ -213,6 +269,12 @@ class STAGE(nn.Module):
         self.t_iter = opt.t_iter
         self.extra_span_length = opt.extra_span_length
         self.add_local = opt.add_local
+        # model/stage.py:390 max_num_proposal: how many predicted spans of the ground-truth candidate may train the classifier next
+        # to the label's span.  1 (the reference's default, and an opt without the attribute): the arg-max kernel; 2 .. 8: the top-K
+        # kernel (csrc/topk_spans.hip)
+        self.max_num_proposal = int(getattr(opt, "max_num_proposal", 1))
+        if not 1 <= self.max_num_proposal <= 8:
+            raise ValueError("opt.max_num_proposal must be in 1 .. 8, got %r" % (self.max_num_proposal,))
         self.use_sup_att = opt.use_sup_att
         self.num_negatives = opt.num_negatives
         self.negative_pool_size = opt.negative_pool_size
@@ -528,6 +590,9 @@ class STAGE(nn.Module):
         N, NA, Li, D = max_statement.shape
         x = max_statement.reshape(N * NA, Li, D)
         m = max_statement_mask.reshape(N * NA, Li)
+        if self.training and self.max_num_proposal > 1:
+            return self._get_proposals_topk(max_statement, max_statement_mask, temporal_scores, targets, ts_labels, iou_thd,
+                                            ce_prob_thd, extra_span_length, gt_scores_fn)
         if self.training:
             # ground-truth candidate's scores (:408-409); with the candidates of an example spread over a rank group they
             # come from the rank that holds it (parallel.CandidateLayout.gt_scores)
@@ -567,7 +632,8 @@ class STAGE(nn.Module):
                     wins.append((max(0, s - extra_span_length), e + extra_span_length))
             src_t = torch.tensor(src, device=x.device, dtype=torch.long)
             win_t = torch.tensor(wins, device=x.device, dtype=torch.int32)       # (N_new, 2)
-            # index_select (backward: one index_add; at most two contributions per slot, so the order cannot matter)
+            # index_select (backward: one index_add; at most two contributions per slot here -- max_num_proposal = 1 -- so the
+            # order cannot matter; more proposals per example: _get_proposals_topk sums in a fixed order)
             # instead of advanced indexing (backward: sort-based index_put, five small kernels each)
             xg = max_statement.index_select(0, src_t).reshape(-1, Li, D)          # (N_new*5, Li, D)
             mg = max_statement_mask.reshape(N, NA, Li).index_select(0, src_t).reshape(-1, Li)
@@ -581,6 +647,45 @@ class STAGE(nn.Module):
         win = torch.stack([(st - extra_span_length).clamp(min=0), ed + 1 + extra_span_length], dim=1).int().contiguous()
         loc = ops.masked_max(x, m, win)
         return torch.cat([loc, glob], dim=-1).view(N, NA, 2 * D), targets
+
+    def _read_spans(self, spans, then):
+        """One copy of the span table to the pinned landing buffer; ``then()`` is queued behind it and runs while the host waits for
+        the event.  Returns (rows of Python floats, then())."""
+        if self._span_host is None or self._span_host.shape != spans.shape:
+            self._span_host = torch.empty(spans.shape, dtype=torch.float32, pin_memory=True)
+        with torch.cuda.device(spans.device):
+            self._span_host.copy_(spans, non_blocking=True)
+            arrived = torch.cuda.Event()
+            arrived.record(torch.cuda.current_stream(spans.device))
+            res = then()
+            arrived.synchronize()
+        return self._span_host.tolist(), res
+
+    def _get_proposals_topk(self, max_statement, max_statement_mask, temporal_scores, targets, ts_labels, iou_thd, ce_prob_thd,
+                            extra_span_length, gt_scores_fn):
+        """get_proposals in training with max_num_proposal = k > 1 on the per-op path: the k best spans of the ground-truth candidate
+        from the top-K kernel, one read-back of (3k + 3) N floats, ``proposal_rows`` on the host, then the pooling ops."""
+        N, NA, Li, D = max_statement.shape
+        k = self.max_num_proposal
+        x = max_statement.reshape(N * NA, Li, D)
+        m = max_statement_mask.reshape(N * NA, Li)
+        if gt_scores_fn is not None:
+            # candidate-sharded batches: the scores come from the rank that holds the candidate (parallel.CandidateLayout.gt_scores)
+            span, conf = groups.topk_spans(gt_scores_fn(temporal_scores, targets).detach().float(), k)
+            ranks = torch.cat([span.float(), conf.unsqueeze(2)], dim=2).reshape(N, 3 * k).t()
+            dev_spans = torch.cat([ranks, torch.stack([ts_labels["st"].float(), ts_labels["ed"].float(), targets.float()])]).contiguous()
+        else:
+            dev_spans = groups.gt_spans_topk(temporal_scores.float(), targets, ts_labels["st"], ts_labels["ed"], k)
+        host, glob = self._read_spans(dev_spans, lambda: ops.masked_max(x, m))
+        src, wins, inv, _ = proposal_rows(host, N, k, iou_thd, ce_prob_thd, extra_span_length)
+        src_t = torch.tensor(src, device=x.device, dtype=torch.long)
+        inv_t = torch.tensor(inv, device=x.device, dtype=torch.long).view(N, k + 1)
+        wg = torch.tensor(wins, device=x.device, dtype=torch.int32).view(-1, 1, 2).expand(-1, NA, -1).reshape(-1, 2).contiguous()
+        xg = _GatherExamples.apply(max_statement, src_t, inv_t).reshape(-1, Li, D)          # (N_new*5, Li, D)
+        mg = max_statement_mask.reshape(N, NA, Li).index_select(0, src_t).reshape(-1, Li)
+        loc = ops.masked_max(xg, mg, wg).view(-1, NA, D)
+        pooled = torch.cat([loc, _GatherExamples.apply(glob.view(N, NA, D), src_t, inv_t)], dim=-1)   # (N_new, 5, 2D)
+        return pooled, targets.index_select(0, src_t)
 
     def _linear_wrapper(self, x, lw: _LinearWrapperParams, res=None):
         y, s = self._ln(x, lw.conv[0], drop=True, res=res)
@@ -673,44 +778,27 @@ class STAGE(nn.Module):
         from .att_host import PinnedStage
         N, NA, Li, D = first.shape
         dev = first.device
-        spans = groups.gt_spans(t_scores, targets, ts_labels["st"], ts_labels["ed"])         # (6, N) device floats
-        if self._span_host is None or self._span_host.shape != spans.shape:
-            self._span_host = torch.empty(spans.shape, dtype=torch.float32, pin_memory=True)
+        k = self.max_num_proposal
+        if k == 1:
+            spans = groups.gt_spans(t_scores, targets, ts_labels["st"], ts_labels["ed"])     # (6, N) device floats
+        else:
+            spans = groups.gt_spans_topk(t_scores, targets, ts_labels["st"], ts_labels["ed"], k)      # (3k + 3, N)
         x = first.reshape(N * NA, Li, D)
         m = mx_mask.reshape(N * NA, Li)
-        with torch.cuda.device(dev):
-            self._span_host.copy_(spans, non_blocking=True)
-            arrived = torch.cuda.Event()
-            arrived.record(torch.cuda.current_stream(dev))
-            glob, idx_g = groups.masked_max_raw(x, m)       # queued behind the copy: runs while the host reads the spans
-            arrived.synchronize()
-        host = self._span_host.tolist()
-        src, wins, inv = [], [], [-1] * (2 * N)
-        for n in range(N):
-            gs, ge = int(host[3][n]), int(host[4][n]) + 1
-            cand = [(gs, ge)]
-            if host[2][n] >= ce_prob_thd:
-                ps, pe = int(host[0][n]), int(host[1][n]) + 1
-                inter = max(0, min(pe, ge) - max(ps, gs))
-                union = max(pe, ge) - min(ps, gs)
-                if union != 0 and inter / union >= iou_thd:
-                    cand.append((ps, pe))
-            for j, (s0, e0) in enumerate(cand):
-                inv[2 * n + j] = len(src)
-                src.append(n)
-                wins += [max(0, s0 - extra_span_length), e0 + extra_span_length]
+        # the global max is queued behind the copy: it runs while the host reads the spans
+        host, (glob, idx_g) = self._read_spans(spans, lambda: groups.masked_max_raw(x, m))
+        # the repeated targets travel with the bookkeeping (ATen's index_select switches kernels at 16 indices: the first step
+        # with a 17th proposal paid ~9 ms of lazy kernel loading inside the training loop)
+        src, wins, inv, tgt = proposal_rows(host, N, k, iou_thd, ce_prob_thd, extra_span_length)
         P = len(src)
         if self._meta_stage is None:
             self._meta_stage = PinnedStage()
-        # the repeated targets travel with the bookkeeping (ATen's index_select switches kernels at 16 indices: the first step
-        # with a 17th proposal paid ~9 ms of lazy kernel loading inside the training loop)
-        tgt = [int(host[5][n]) for n in src]
         meta = self._meta_stage.upload(torch.tensor(src + wins + inv + tgt, dtype=torch.int32), dev)
         cl = self.classifier
         seeds = self._seeds(1)
         logits = groups.pool_classifier(x, m, glob, idx_g, meta, (N, NA, Li, D, P), self._p(), seeds,
-                                        [cl.conv[0].weight, cl.conv[0].bias, cl.conv[2].weight, cl.conv[2].bias])
-        return logits, meta[3 * P + 2 * N:].long()
+                                        [cl.conv[0].weight, cl.conv[0].bias, cl.conv[2].weight, cl.conv[2].bias], slots=k + 1)
+        return logits, meta[3 * P + (k + 1) * N:].long()
 
     def get_ts_loss(self, temporal_scores, ts_labels, answer_indices, cand_offset: int = 0):
         """model/stage.py:539-555.  ``cand_offset``: global index of local candidate 0 when the candidates of an example
