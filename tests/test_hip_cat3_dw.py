@@ -1,7 +1,9 @@
 """csrc/cat3_bwd_dw.hip: the backward of  y = ReLU(drop(LN_3D([a, b, a*b])) W^T + c)  (model/stage.py:381-385, :276-279) with the
-Linear's own gradients formed inside -- no saved z.  Held against (i) the kernel it replaces for da / db / d gamma / d beta
-(csrc/cat3_fused.hip: stage_cat3_dx_ln_bwd*, itself pinned against the reference fixtures through the whole-model tests) and (ii) an
-fp64 contraction over the z the forward kernels write for dW / dc.  Through the C ABI, on the GPU."""
+Linear's own gradients formed inside -- no saved z.  Held HERE against (i) the kernel it replaces for da / db / d gamma / d beta
+(csrc/cat3_fused.hip: stage_cat3_dx_ln_bwd*) and (ii) an fp64 contraction over the z the forward kernels write for dW / dc: kernel
+against kernel, with the dropout stream, the fp16 split and the table layouts shared by both sides.  The independent reference of
+both backward kernels and of the fused forward -- every output against a float64 torch restatement -- is tests/test_hip_cat3_fp64.py.
+Through the C ABI, on the GPU."""
 import numpy as np
 import pytest
 import torch

@@ -181,7 +181,8 @@ def test_group_path_issues_few_host_calls(hip_device):
 def test_fused_cat3_backward_equals_gemm_plus_layernorm_backward(hip_device, which, dims, p):
     """csrc/cat3_fused.hip (the Linear's input gradient never leaves the compute unit) against the two-kernel path it replaces
     (dX GEMM -> 3D-wide tensor -> LayerNorm backward): same gradients to fp32 rounding (both products are the two-way fp16 split;
-    the summation orders differ)."""
+    the summation orders differ).  Kernel against kernel: the independent fp64 reference of the fused backward kernels is
+    tests/test_hip_cat3_fp64.py."""
     import os
     from tvqaplus_amd import groups
     g = torch.Generator().manual_seed(7)
@@ -244,7 +245,8 @@ def test_fused_cat3_forward_equals_layernorm_plus_gemm(hip_device, rep, inner, G
     """csrc/cat3_fused.hip, forward: LayerNorm([a, b, a*b]) -> dropout -> Linear -> ReLU in one pass against the two kernels it
     replaces.  z, mean, rstd: same arithmetic in the same order (identical up to one ulp of multiply-add contraction, the dropout mask
     identical); y to fp32 rounding (both products are the two-way fp16
-    split, summed in different orders); the ReLU bit masks agree wherever |y| is not rounding noise."""
+    split, summed in different orders); the ReLU bit masks agree wherever |y| is not rounding noise.  Kernel against kernel: the
+    independent fp64 reference of the fused forward is tests/test_hip_cat3_fp64.py."""
     from tvqaplus_amd import _lib
     lib = _lib.load()
     D = 128

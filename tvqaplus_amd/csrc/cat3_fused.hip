@@ -762,7 +762,7 @@ __global__ __launch_bounds__(256, 3) void cff_fwd_kernel(const float* __restrict
         typedef unsigned cf_u4 __attribute__((ext_vector_type(4)));
         cf_u4 ra[4], rb[4];
         // broadcast operand: row -> (row / (rep * inner)) * inner + row % inner.  Uniform part once per tile, per row an add and
-        // at most three conditional subtractions (inner >= 11)
+        // at most three conditional subtractions (inner >= 11) and one group step (rep * inner >= 32): ..._fwd_supported holds both
         const long g0 = rep > 1 ? t0 / GR : 0;
         const int r0 = rep > 1 ? (int)(t0 - g0 * GR) : 0, p0 = rep > 1 ? r0 % inner : 0;
         if (RAG) {
@@ -912,8 +912,9 @@ __global__ __launch_bounds__(256, 3) void cff_fwd_kernel(const float* __restrict
 
 extern "C" int stage_cat3_ln_gemm_fwd_supported(long long rows, int D, int rep, int inner) {
     if (getenv("STAGE_NO_CAT3_FUSED") || getenv("STAGE_NO_CAT3_FUSED_FWD")) return 0;
-    return (D == CF_D && rows >= 4096 && rows * 3ll * D * 4 < (1ll << 31) && rep >= 1 && inner >= 1 && (rep == 1 || inner >= 11) &&
-            rows % ((long long)rep * inner) == 0) ? 1 : 0;
+    // broadcast `a`: the kernel takes at most three steps of `inner` and ONE group step inside a 32-row tile
+    return (D == CF_D && rows >= 4096 && rows * 3ll * D * 4 < (1ll << 31) && rep >= 1 && inner >= 1 &&
+            (rep == 1 || (inner >= 11 && (long long)rep * inner >= 32)) && rows % ((long long)rep * inner) == 0) ? 1 : 0;
 }
 extern "C" size_t stage_cat3_ln_gemm_fwd_ws_bytes(void) { return cf_align((size_t)CFF_WFRAG * sizeof(uint4)) + 256; }
 extern "C" int stage_cat3_ln_gemm_fwd_rag_supported(long long rows, long long a_rows, long long b_rows, int D) {
