@@ -540,6 +540,19 @@ int stage_rag_rowinfo(const int* seq, const int* seqfc, long long S, int Lqa, in
  * tensor that compact row r reads (stage_rag_ctx_rows).  The *_gather entry points are LayerNorm / L2 normalisation reading those rows
  * in place (model/stage.py:85-91, 98-104, 256); everything behind them runs on the compact rows. */
 int stage_rag_ctx_rows(const int* cq, long long frames, int L, int* src_rows, void* stream);
+/* Packed context features (csrc/packed.hip, tvqaplus_amd/packed.py): a stream arrives as the rows that exist -- frame-major, frame f
+ * owning packed rows ptab[f].x .. ptab[f].x + ptab[f].y - 1 (ptab (frames, 2) int32: first packed row, len <= L) -- followed by ONE zero
+ * row, the source of every padded position (the collate zero-fills behind a frame's length: tvqa_dataset.py:515-553).
+ * stage_pack_ctx_rows: stage_rag_ctx_rows for such a stream -- src_rows[cq[f].x + l] = l < ptab[f].y ? ptab[f].x + l : zero_row for
+ * l < cq[f].y; the *_rag input-MLP groups then read the packed buffer through the table.  L < 1 or frames * L >= 2^31:
+ * STAGE_ERR_SHAPE, nothing launched.
+ * stage_pack_unpack: the padded image for the paths that keep dense tensors.  EVERY row of dense (frames, L, row_bytes) is written in
+ * one pass: row l < len is a byte copy of packed row start + l, every other row is zeros (no memset needed, any element type);
+ * mask != NULL: the (frames, L) fp32 prefix mask as well; packed == dense == NULL: the mask alone.  row_bytes % 8 == 0,
+ * 8 <= row_bytes <= 4096, 8-byte aligned bases (16-byte accesses when row_bytes % 16 == 0 and both bases are 16-byte aligned),
+ * frames * L < 2^31 -- anything else is STAGE_ERR_SHAPE before a launch. */
+int stage_pack_ctx_rows(const int* cq, const int* ptab, long long frames, int L, int zero_row, int* src_rows, void* stream);
+int stage_pack_unpack(const void* packed, const int* ptab, void* dense, float* mask, long long frames, int L, int row_bytes, void* stream);
 int stage_layernorm_gather_fwd(const float* x, const int* gather, const float* gamma, const float* beta, float* y, float* mean,
                                float* rstd, long long rows, int K, float eps, float p_drop, unsigned long long seed, void* stream);
 int stage_layernorm_gather_bwd(const float* dy, const float* x, const int* gather, const float* mean, const float* rstd,

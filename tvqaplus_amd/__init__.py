@@ -9,6 +9,7 @@ Layout (only what the path needs):
 * ``stage.py``     ``STAGE``: constructor / forward / state_dict compatible with the reference's model/stage.py
 * ``att_host.py``  host side of the supervised-attention loss (reference model/stage.py:344-407)
 * ``parallel.py``  one-process-per-GPU sharding of the batch and of the 5 answer candidates, flat gradient bucket
+* ``packed.py``    context features without their padding (``PackedFeatures``): the collate, the host specification of the unpad
 * ``prefetch.py``  pinned double-buffered host->HBM batch feed
 * ``evaluation.py``span selection, prediction writer and the reference's temporal / grounding metrics
 * ``synth.py``     synthetic batches of the BASELINE.json shapes

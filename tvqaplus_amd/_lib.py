@@ -159,6 +159,9 @@ SIGNATURES = {
     "stage_str_attn_fwd_fc": (I, [P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, F, U64, P]),
     "stage_str_attn_bwd_fused_fc": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, SZ, P]),
     "stage_rag_ctx_rows": (I, [P, LL, I, P, P]),
+    # packed context features (csrc/packed.hip; tvqaplus_amd/packed.py): the source-row table into a packed buffer, the padded image / mask
+    "stage_pack_ctx_rows": (I, [P, P, LL, I, I, P, P]),
+    "stage_pack_unpack": (I, [P, P, P, P, LL, I, I, P]),
     "stage_layernorm_gather_fwd": (I, [P, P, P, P, P, P, P, LL, I, F, F, U64, P]),
     "stage_layernorm_gather_bwd": (I, [P, P, P, P, P, P, P, P, LL, I, F, U64, P, SZ, P]),
     "stage_l2norm_gather_fwd": (I, [P, P, P, LL, I, F, P]),

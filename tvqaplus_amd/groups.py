@@ -519,7 +519,8 @@ class _InputMLPRag(torch.autograd.Function):
 
 def input_mlp_rag(x, clay, l2: bool, p: float, seeds, params):
     """As ``input_mlp`` on the compact rows of a ragged context stream: x the padded (..., K0) features, ``clay.src_rows`` the rows of it
-    that exist; -> (clay.U, D).  Half-precision x: as ``input_mlp``."""
+    that exist; -> (clay.U, D).  Half-precision x: as ``input_mlp``.  A packed stream (tvqaplus_amd/packed.py) hands over its
+    ``(P + 1, K0)`` rows instead: the layout's source rows then point into that buffer, its zero row included."""
     return _InputMLPRag.apply(x, clay, int(bool(l2)), p, tuple(seeds), *params)
 
 

@@ -29,6 +29,8 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import torch
 import torch.distributed as dist
 
+from .packed import PackedFeatures
+
 
 def init_from_env(backend: Optional[str] = None) -> Tuple[int, int, int]:
     """RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* come from torch.distributed.run.  Returns (rank, local_rank, world)."""
@@ -104,6 +106,8 @@ def shard_batch(batch, rank: int, world: int):
     for k, v in batch.items():
         if k in _TENSOR_KEYS and torch.is_tensor(v):
             out[k] = v[lo:hi]
+        elif k in _TENSOR_KEYS and isinstance(v, PackedFeatures):     # a packed context stream: the rows of these examples + the zero row
+            out[k] = v.slice_examples(lo, hi)
         elif k == "ts_label" and isinstance(v, dict):
             out[k] = {kk: vv[lo:hi] for kk, vv in v.items()}
         elif k in _LIST_KEYS and isinstance(v, list):
@@ -361,6 +365,8 @@ class CandidateLayout:
                 out[k] = v[lo:hi, k0:k1].contiguous()
             elif k in _TENSOR_KEYS and torch.is_tensor(v):
                 out[k] = v[lo:hi]
+            elif k in _TENSOR_KEYS and isinstance(v, PackedFeatures):
+                out[k] = v.slice_examples(lo, hi)
             elif k == "ts_label" and isinstance(v, dict):
                 out[k] = {kk: vv[lo:hi] for kk, vv in v.items()}
             elif k in _LIST_KEYS and isinstance(v, list):

@@ -10,6 +10,10 @@ over PCIe Gen5 x16 -- more than half of the 24 ms step.  ``BatchPrefetcher`` mov
 
 Non-tensor fields (qid lists, att_labels, boxes, ...) pass through untouched.
 
+A context stream that comes as ``tvqaplus_amd.packed.PackedFeatures`` (no padding: less than half the bytes at the full
+configuration) is staged the same way: its ``data`` goes through the pinned buffers, ``feature_dtype`` applies to it, its lengths stay
+on the host.
+
 ``feature_dtype=torch.bfloat16`` (for a model built with ``opt.storage_dtype = "bf16"``) rounds the three feature tensors
 (``qas_bert``, ``sub_bert``, ``vid``) to bf16 while they are copied into the pinned staging buffers: the model would round them
 on entry anyway, and the transfer is 431 MB instead of 862 MB.  Masks, labels and indices keep their types.
@@ -25,16 +29,21 @@ from typing import Dict, Iterable, Iterator, Optional
 
 import torch
 
+from .packed import PackedFeatures
+
 
 class BatchPrefetcher:
     FEATURES = ("qas_bert", "sub_bert", "vid")
 
-    def __init__(self, batches: Iterable, device, depth: int = 2, feature_dtype: Optional[torch.dtype] = None):
+    def __init__(self, batches: Iterable, device, depth: int = 2, feature_dtype: Optional[torch.dtype] = None, stream=None):
+        """``stream``: the copy stream (default: a new one).  A process that builds several prefetchers one after the other (one per
+        epoch, tools/packed_h2d_time.py) hands all of them the same stream: every new stream is mapped onto one of a few hardware
+        queues, and a copy stream that lands on the queue of a compute stream no longer overlaps the step."""
         if not torch.cuda.is_available():
             raise RuntimeError("BatchPrefetcher needs a GPU (the HIP path has no CPU fallback)")
         self.src = iter(batches)
         self.device = torch.device(device)
-        self.side = torch.cuda.Stream(device=self.device)
+        self.side = torch.cuda.Stream(device=self.device) if stream is None else stream
         self.depth = max(2, int(depth))
         if feature_dtype not in (None, torch.float32, torch.float16, torch.bfloat16):
             raise ValueError("feature_dtype must be None, torch.float32, torch.float16 or torch.bfloat16")
@@ -77,6 +86,10 @@ class BatchPrefetcher:
             for k, v in host.items():
                 if torch.is_tensor(v):
                     out[k] = self._stage(slot, k, v).to(self.device, non_blocking=True)
+                elif isinstance(v, PackedFeatures):
+                    # a packed context stream: its rows (and the zero row) go through the staging set like a feature tensor, the
+                    # lengths stay on the host
+                    out[k] = PackedFeatures(self._stage(slot, k, v.data).to(self.device, non_blocking=True), v.lens, v.L)
                 elif isinstance(v, dict):
                     out[k] = {kk: (self._stage(slot, k + "." + kk, vv).to(self.device, non_blocking=True)
                                    if torch.is_tensor(vv) else vv) for kk, vv in v.items()}
@@ -105,7 +118,7 @@ class BatchPrefetcher:
         cur = torch.cuda.current_stream(self.device)
         cur.wait_event(done)
         for v in batch.values():
-            if torch.is_tensor(v):
+            if torch.is_tensor(v) or isinstance(v, PackedFeatures):
                 v.record_stream(cur)
             elif isinstance(v, dict):
                 for vv in v.values():

@@ -239,17 +239,34 @@ class CtxTables:
             out[s:s + n] = f * self.L + np.arange(n)
         return out
 
+    def src_rows_packed_host(self, ptab: np.ndarray, zero_row: int) -> np.ndarray:
+        """What stage_pack_ctx_rows computes on the device for a PACKED stream (tvqaplus_amd/packed.py: ``ptab`` (frames, 2) = first
+        packed row, len; ``zero_row`` = P): the rows of the packed buffer the compact rows read -- a frame's own rows below its
+        length, the zero row for the halo positions behind it (tests/test_hip_packed.py holds the kernel to this, row for row)."""
+        out = np.empty(self.U, dtype=np.int32)
+        for f in range(self.cq.shape[0]):
+            s, n = int(self.cq[f, 0]), int(self.cq[f, 1])
+            l = np.arange(n)
+            out[s:s + n] = np.where(l < int(ptab[f, 1]), int(ptab[f, 0]) + l, int(zero_row))
+        return out
+
 
 class CtxLayout:
     """Device side of ``CtxTables``: the tables, the source-row table, and the table-pointer array the ragged encoder group takes."""
     out_rows = 0          # (the encoder group does not pool over these sequences)
 
-    def __init__(self, tab: CtxTables, device, stage=None):
+    def __init__(self, tab: CtxTables, device, stage=None, packed=None):
+        """``packed`` (tvqaplus_amd.packed.PackedFeatures): the stream arrives without its padding -- its frame table rides in the same
+        upload and the source rows point into ``packed.data`` (the zero row for the halo positions behind a frame's length)."""
         self.tab = tab
         self.N, self.Li, self.Lqa = tab.N, tab.Li, tab.L       # Lqa: the longest sequence, under the name the encoder group uses
         self.U, self.S = tab.U, tab.S
         self.Ucap = max(CAP_STEP, _align(tab.U, CAP_STEP))
         parts = [tab.cq.reshape(-1), tab.seq.reshape(-1), tab.live_frames]
+        self.packed = packed
+        if packed is not None:
+            assert (packed.N, packed.Li, packed.L) == (tab.N, tab.Li, tab.L)
+            parts.append(packed.ptab().reshape(-1))
         offs, total = [], 0
         for p in parts:
             offs.append(total)
@@ -269,16 +286,50 @@ class CtxLayout:
         self.seq = self.tables[offs[1]: offs[1] + tab.seq.size]
         self.live_frames = self.tables[offs[2]: offs[2] + tab.live_frames.size]     # (S,) frame index of every sequence
         self.regular = tab.regular
+        self.ptab = self.tables[offs[3]: offs[3] + 2 * tab.N * tab.Li] if packed is not None else None
         self.src_rows = torch.empty(max(self.U, 1), dtype=torch.int32, device=device)
         if self.tables.is_cuda and self.U > 0:
             from .ops import _stream
             with torch.cuda.device(device):
-                _lib.check(_lib.load().stage_rag_ctx_rows(self.cq.data_ptr(), tab.N * tab.Li, tab.L, self.src_rows.data_ptr(), _stream()),
-                           "stage_rag_ctx_rows")
+                if packed is not None:
+                    _lib.check(_lib.load().stage_pack_ctx_rows(self.cq.data_ptr(), self.ptab.data_ptr(), tab.N * tab.Li, tab.L, packed.P,
+                                                               self.src_rows.data_ptr(), _stream()), "stage_pack_ctx_rows")
+                else:
+                    _lib.check(_lib.load().stage_rag_ctx_rows(self.cq.data_ptr(), tab.N * tab.Li, tab.L, self.src_rows.data_ptr(), _stream()),
+                               "stage_rag_ctx_rows")
         self.T = (ctypes.c_void_p * 4)(None, None, self.seq.data_ptr(), None)
 
     def device_tensors(self) -> list:
         return [self.tables, self.src_rows]
+
+    def prefix_mask(self) -> torch.Tensor:
+        """(N, Li, L) fp32 prefix mask of a packed stream that came without one: the mask-only call of stage_pack_unpack on the frame
+        table that is already on the device."""
+        return packed_mask(self.ptab, self.N, self.Li, self.Lqa)
+
+
+def packed_mask(ptab: torch.Tensor, N: int, Li: int, L: int) -> torch.Tensor:
+    """(N, Li, L) fp32 prefix mask from the device frame table ``ptab`` of a packed stream (csrc/packed.hip)."""
+    from .ops import _stream
+    mask = torch.empty(N, Li, L, dtype=torch.float32, device=ptab.device)
+    with torch.cuda.device(ptab.device):
+        _lib.check(_lib.load().stage_pack_unpack(None, ptab.data_ptr(), None, mask.data_ptr(), N * Li, L, 0, _stream()),
+                   "stage_pack_unpack (mask)")
+    return mask
+
+
+def packed_unpack(packed, ptab: torch.Tensor, with_mask: bool):
+    """The padded (N, Li, L, K) image of a packed stream on its device, and its (N, Li, L) fp32 prefix mask when ``with_mask``: ONE
+    pass that writes every row (csrc/packed.hip: stage_pack_unpack) -- for the paths that keep dense context tensors."""
+    from .ops import _stream
+    N, Li, L, K = packed.shape
+    data = packed.data
+    dense = torch.empty(N, Li, L, K, dtype=data.dtype, device=data.device)
+    mask = torch.empty(N, Li, L, dtype=torch.float32, device=data.device) if with_mask else None
+    with torch.cuda.device(data.device):
+        _lib.check(_lib.load().stage_pack_unpack(data.data_ptr(), ptab.data_ptr(), dense.data_ptr(), None if mask is None else mask.data_ptr(),
+                                                 N * Li, L, K * data.element_size(), _stream()), "stage_pack_unpack")
+    return dense, mask
 
 
 def mask_lens(mask: np.ndarray) -> np.ndarray:

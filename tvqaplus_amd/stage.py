@@ -23,6 +23,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import groups, ops, ragged
+from .packed import PackedFeatures
 
 NEG = -1e10
 
@@ -366,6 +367,7 @@ class STAGE(nn.Module):
         self.last_ragged_ctx: Dict[str, ragged.CtxLayout] = {}
         self._rag_stage = None
         self._ctx_stage: Dict[str, object] = {}
+        self._ptab_stage: Dict[str, object] = {}      # pinned staging of a packed stream's frame table when no layout carries it
         # storage type of the activations between kernels: fp32 (the reference's), or bf16 with ``opt.storage_dtype = "bf16"``
         # (BASELINE.json configs[4]: bf16 weights / activations, fp32 softmax / statistics / accumulation; parameters stay
         # fp32 master copies, a weight is rounded to bf16 when a GEMM stages it; scores, losses and logits are fp32)
@@ -496,10 +498,14 @@ class STAGE(nn.Module):
                      feat16=True):
         """model/stage.py:350-363 (+ the F.normalize of :256 when l2_normalize).  ``data`` may be fp16 / bf16 in the fp32 model: the
         input-MLP group reads such features in place (``feat16``; csrc/feat16.hip), every other path upcasts them first."""
-        M, L, _ = data.shape
+        if clay is None:
+            M, L, _ = data.shape
+        else:
+            L = clay.Lqa       # (a packed stream hands its (P + 1, K) rows over: the padded row length is the layout's)
         if clay is not None:
-            # ragged context rows (tvqaplus_amd/ragged.py: CtxLayout): the MLP reads the live rows of the padded features in place,
-            # everything behind it -- and the attention -- runs on the compact rows
+            # ragged context rows (tvqaplus_amd/ragged.py: CtxLayout): the MLP reads the live rows of the padded features in place
+            # (of a packed stream: its rows and its zero row, through the same table), everything behind it -- and the attention --
+            # runs on the compact rows
             params = [init_encoder[0].weight, init_encoder[0].bias, init_encoder[2].weight, init_encoder[2].bias,
                       init_encoder[4].weight, init_encoder[4].bias, downsize_encoder[1].weight, downsize_encoder[1].bias,
                       downsize_encoder[3].weight, downsize_encoder[3].bias]
@@ -831,6 +837,19 @@ class STAGE(nn.Module):
         (batch.mask_host) or ONE read-back of the device masks; cached for the forward."""
         if self._mask_info is not None:
             return self._mask_info
+        pk = {k: f for k, f in ((k, batch.sub_bert if k == "sub" else batch.vid) for k in names) if isinstance(f, PackedFeatures)}
+        if pk:
+            # packed streams carry their lengths on the host: nothing of them is ever read back
+            mh = dict(_opt(batch, "mask_host", None) or {})
+            for k, f in pk.items():
+                if mh.get(k + "_len") is None or mh[k + "_len"].shape != (N, Li):
+                    mh[k + "_len"] = f.lens
+            need = [k for k in names if mh.get(k + "_len") is None or mh[k + "_len"].shape != (N, Li)]
+            if mh.get("qas") is None or mh["qas"].shape != (N, NA, Lqa) or need:
+                mh.update(ragged.info_from_device(batch.qas_mask.view(N, NA, Lqa),
+                                                  {k: (batch.sub_mask if k == "sub" else batch.vid_mask).view(N, Li, -1) for k in need}))
+            self._mask_info = mh
+            return mh
         info = ragged.host_info(batch)
         if info is not None and (info["qas"].shape != (N, NA, Lqa)
                                  or any(info.get(k + "_len") is None or info[k + "_len"].shape != (N, Li) for k in names)):
@@ -874,6 +893,19 @@ class STAGE(nn.Module):
             return torch.zeros(M, L, self.hsz, device=data.device, dtype=self.storage)
         return _ScatterBuckets.apply(M, L, idxs, *ys)
 
+    def _unpack_stream(self, name, pf, with_mask):
+        """The padded image of packed stream ``name`` (and its prefix mask) on the device: one small table upload, one pass
+        (ragged.packed_unpack).  Host features (host-logic tests) unpad on the host."""
+        if not pf.is_cuda:
+            dense, mask = pf.unpad_host()
+            return dense, (mask if with_mask else None)
+        from .att_host import PinnedStage
+        st = self._ptab_stage.get(name)
+        if st is None:
+            st = self._ptab_stage[name] = PinnedStage()
+        ptab = st.upload(pf.ptab().reshape(-1), pf.device)
+        return ragged.packed_unpack(pf, ptab, with_mask)
+
     def _ragged_layout(self, batch, qas_mask, a_embed):
         """The ragged layout of this batch (tvqaplus_amd/ragged.py), or None when the dense path runs: switched off, a configuration
         the ragged kernels do not cover (decided BEFORE anything is launched: hsz = 128 on the K-group path, one classifier-encoder
@@ -900,9 +932,9 @@ class STAGE(nn.Module):
                 cls_halo = min(Lqa, ragged.conv_halo(1, blocks[0].n_conv, k))
         streams = []
         if self.sub_flag:
-            streams.append((batch.sub_mask, batch.sub_bert.shape[1], batch.sub_bert.shape[2]))
+            streams.append((_opt(batch, "sub_mask"), batch.sub_bert.shape[1], batch.sub_bert.shape[2]))
         if self.vfeat_flag:
-            streams.append((batch.vid_mask, batch.vid.shape[1], batch.vid.shape[2]))
+            streams.append((_opt(batch, "vid_mask"), batch.vid.shape[1], batch.vid.shape[2]))
         if not streams or any(Li != streams[0][1] for _, Li, _ in streams):
             return none
         Li = streams[0][1]
@@ -936,8 +968,9 @@ class STAGE(nn.Module):
             halo = sum(ragged.conv_halo(1, b.n_conv, ik) for b in iblocks) if conv_only else 1 << 20
             for (mask, _, L), name in zip(streams, names):
                 feat = batch.sub_bert if name == "sub" else batch.vid
+                pf = feat if isinstance(feat, PackedFeatures) else None
                 if feat.dtype in (torch.float16, torch.bfloat16):
-                    if not groups.feat16_ok(feat):      # (the stream then runs padded, on the upcast features)
+                    if not groups.feat16_ok(feat if pf is None else pf.data):      # (the stream then runs padded, on the upcast features)
                         continue
                 elif feat.dtype != torch.float32 or feat.shape[-1] % 4 or feat.shape[-1] > 1024 or not feat.is_contiguous():
                     continue
@@ -945,7 +978,7 @@ class STAGE(nn.Module):
                 if ct.U == 0:
                     continue
                 st = self._ctx_stage.get(name)
-                clays[name] = ragged.CtxLayout(ct, a_embed.device, st)
+                clays[name] = ragged.CtxLayout(ct, a_embed.device, st) if pf is None else ragged.CtxLayout(ct, a_embed.device, st, packed=pf)
                 self._ctx_stage[name] = clays[name].stage
         return lay, clays
 
@@ -1043,8 +1076,19 @@ class STAGE(nn.Module):
         qas_mask = batch.qas_mask.view(N, NA, -1).float()
         # (all masks converted HERE, on the caller's stream and in front of the first join: a cast issued later on the main stream would
         # not be ordered against a branch stream that reads it)
-        sub_mask_f = batch.sub_mask.float() if self.sub_flag else None
-        vid_mask_f = batch.vid_mask.float() if self.vfeat_flag else None
+        sub_feat = batch.sub_bert if self.sub_flag else None
+        vid_feat = batch.vid if self.vfeat_flag else None
+        # packed streams (tvqaplus_amd/packed.py) may come without their masks: those are built on the device behind the layout decision,
+        # on the stream that consumes them
+        packed = {k: f for k, f in (("sub", sub_feat), ("vid", vid_feat)) if isinstance(f, PackedFeatures)}
+        if packed:
+            sub_mask_f = _opt(batch, "sub_mask") if self.sub_flag else None
+            vid_mask_f = _opt(batch, "vid_mask") if self.vfeat_flag else None
+            sub_mask_f = sub_mask_f.float() if torch.is_tensor(sub_mask_f) else None
+            vid_mask_f = vid_mask_f.float() if torch.is_tensor(vid_mask_f) else None
+        else:
+            sub_mask_f = batch.sub_mask.float() if self.sub_flag else None
+            vid_mask_f = batch.vid_mask.float() if self.vfeat_flag else None
         dev = batch.qas_bert.device
         qas_arrived = None
         if self.inference_mode and self.vfeat_flag and torch.is_tensor(batch.qas) and batch.qas.is_cuda:
@@ -1079,6 +1123,29 @@ class STAGE(nn.Module):
         lay, clays = self._ragged_layout(batch, qas_mask, a_embed)
         self.last_ragged, self.last_ragged_ctx = lay, clays
         self.last_buckets = {}
+        unpacked = []
+        for name, pf in packed.items():
+            # decided: a stream its ragged layout took is read in place through the layout's source rows; any other path (bucket plan,
+            # bf16 storage, fuse_input_ln, the per-op path, use_ragged = False) gets the padded image, built HERE, once, on the device,
+            # and proceeds exactly as with a padded batch.  A missing mask comes out of the same frame table.
+            need_mask = (sub_mask_f if name == "sub" else vid_mask_f) is None
+            cl_ = clays.get(name)
+            mask = None
+            if cl_ is not None:
+                if need_mask and not (name == "vid" and streams >= 2):
+                    mask = cl_.prefix_mask()           # (the video stream's: on its branch stream, below)
+            else:
+                dense, mask = self._unpack_stream(name, pf, need_mask)
+                unpacked.append(dense)
+                if name == "sub":
+                    sub_feat = dense
+                else:
+                    vid_feat = dense
+            if mask is not None:
+                if name == "sub":
+                    sub_mask_f = mask
+                else:
+                    vid_mask_f = mask
         if streams:
             s_vid.wait_stream(main)                # the layouts' tables are uploaded / expanded on the main stream
             # Everything allocated on the main stream that a branch stream reads -- in the forward or, through saved tensors, in the
@@ -1086,7 +1153,7 @@ class STAGE(nn.Module):
             # the allocator for both side streams, so that a block whose last reference is dropped by a side-stream node is not handed
             # to the main stream's next allocation while that node's kernel still reads it (the statement / video
             # embeddings and the level-3 outputs are registered where they cross).
-            shared = [qas_mask, sub_mask_f, vid_mask_f]
+            shared = [qas_mask, sub_mask_f, vid_mask_f] + unpacked
             if lay is not None:
                 shared += lay.device_tensors()
             for cl_ in clays.values():
@@ -1096,16 +1163,17 @@ class STAGE(nn.Module):
                     t.record_stream(s_qa)
                     t.record_stream(s_vid)
         if self.sub_flag:
-            Li, Lw = batch.sub_bert.shape[1:3]
+            Li, Lw = sub_feat.shape[1:3]
             sub_mask = sub_mask_f.view(N, Li, Lw)
             cl = clays.get("sub")
             plan = self._ctx_buckets(batch, "sub", N, NA, qas_mask.shape[-1], Li, Lw) if cl is None else None
             if plan is not None:
                 self.last_buckets["sub"] = [(len(ix), lb) for ix, lb in plan]
-                sub_embed = self._base_encoder_buckets(plan, batch.sub_bert.view(N * Li, Lw, -1), sub_mask.view(N * Li, Lw),
+                sub_embed = self._base_encoder_buckets(plan, sub_feat.view(N * Li, Lw, -1), sub_mask.view(N * Li, Lw),
                                                        self.bert_word_encoding_fc, self.input_embedding, self.input_encoder, False)
             else:
-                sub_embed = self.base_encoder(batch.sub_bert.view(N * Li, Lw, -1), sub_mask.view(N * Li, Lw),
+                sub_embed = self.base_encoder(sub_feat.data if isinstance(sub_feat, PackedFeatures) else sub_feat.view(N * Li, Lw, -1),
+                                              sub_mask.view(N * Li, Lw),
                                               self.bert_word_encoding_fc, self.input_embedding, self.input_encoder, clay=cl)
             if streams:
                 main.wait_stream(s_qa)             # the statement embedding
@@ -1114,17 +1182,24 @@ class STAGE(nn.Module):
                 a_embed, sub_embed if cl is not None else sub_embed.view(N, Li, Lw, D), qas_mask, sub_mask, lay, cl)
             other_outputs["sub_normalized_s"], other_outputs["sub_raw_s"] = norm, raw
         if self.vfeat_flag:
-            Li, Lr = batch.vid.shape[1:3]
+            Li, Lr = vid_feat.shape[1:3]
+            if vid_mask_f is None:
+                # a packed stream without a mask, taken by its ragged layout: the mask is built on the stream that consumes it; the
+                # main stream reads it behind the join (statement mask, classifier head, their backward)
+                with torch.cuda.stream(s_vid):
+                    vid_mask_f = clays["vid"].prefix_mask()
+                vid_mask_f.record_stream(main)
             vid_mask = vid_mask_f.view(N, Li, Lr)
             cl = clays.get("vid")
             plan = self._ctx_buckets(batch, "vid", N, NA, qas_mask.shape[-1], Li, Lr) if cl is None else None
             with (torch.cuda.stream(s_vid) if streams >= 2 else contextlib.nullcontext()):
                 if plan is not None:
                     self.last_buckets["vid"] = [(len(ix), lb) for ix, lb in plan]
-                    vid_embed = self._base_encoder_buckets(plan, batch.vid.view(N * Li, Lr, -1), vid_mask.view(N * Li, Lr), self.vid_fc,
+                    vid_embed = self._base_encoder_buckets(plan, vid_feat.view(N * Li, Lr, -1), vid_mask.view(N * Li, Lr), self.vid_fc,
                                                            self.input_embedding, self.input_encoder, True)
                 else:
-                    vid_embed = self.base_encoder(batch.vid.view(N * Li, Lr, -1), vid_mask.view(N * Li, Lr), self.vid_fc,
+                    vid_embed = self.base_encoder(vid_feat.data if isinstance(vid_feat, PackedFeatures) else vid_feat.view(N * Li, Lr, -1),
+                                                  vid_mask.view(N * Li, Lr), self.vid_fc,
                                                   self.input_embedding, self.input_encoder, l2_normalize=True, clay=cl)
                 if streams >= 3:
                     s_vid.wait_stream(s_qa)
