@@ -499,6 +499,23 @@ int stage_grp_pool_cls_bwd_s(const float* d_logits, const float* mask, const int
                              float* const* grads, float* d_first, const void* arena, size_t arena_bytes, void* tmp, size_t tmp_bytes,
                              int N, int NA, int Li, int D, long long P, int slots, float p_drop, const unsigned long long* seeds,
                              void* stream);
+/* The proposal decision of get_proposals in training (model/stage.py:411-438; model/model_utils.py:37-89) on the device, at a fixed
+ * capacity: no read-back of the span table, no data-dependent row count (csrc/proposals.hip).
+ *   spans     (3K + 3, N) float, what stage_gt_spans (K = 1) / stage_gt_spans_topk write, used as it is
+ *   meta      (5 Pmax) int32 = src[Pmax] | win[2 Pmax] | inv[slots * N] | tgt[Pmax], slots = K + 1, Pmax = slots * N: the layout
+ *             of stage_grp_pool_cls_fwd / _bwd_s with P = Pmax
+ *   rows [0, P): per example the label's span, then every rank with (double)conf >= ce_prob_thd, start >= 0, union != 0 and
+ *             (double)inter / (double)union >= iou_thd (inter / union: integers over end-exclusive spans), in rank order; windows
+ *             [max(0, st - extra), ed + 1 + extra), the upper end unclamped; tgt = the example's answer index
+ *   rows [P, Pmax): src / win of row 0, tgt = -100 (stage_train_loss ignores a negative target); no inv entry names them
+ *   count[0] = P (N <= P <= Pmax), scale[0] = (float)((double)N / (double)P)
+ *   thd_host  HOST array {iou_thd, ce_prob_thd} as double (the one host pointer of the call), read before it returns: the
+ *             comparisons run in double as the host loop's do (a float 0.01f would keep a confidence of np.float32(0.01))
+ * A start / end that is negative, non-finite or >= 2^30 makes its rank absent; no value of the table is used as an index.  One
+ * workgroup, plain stores, bitwise repeatable.  STAGE_ERR_SHAPE before any launch: K outside 1 .. STAGE_TOPK_MAX, N <= 0,
+ * 5 * (K + 1) * N beyond int, extra outside 0 .. 2^20, a NULL pointer.                                                          */
+int stage_proposal_meta(const float* spans, int N, int K, const double* thd_host, int extra, int* meta, int* count, float* scale,
+                        void* stream);
 
 /* G7 evaluation head (model/stage.py:440-448, 526-536 outside training; csrc/eval_head.hip): what get_proposals + the classifier do in
  * eval()/inference for R = N * NA independent rows, forward only.  first (R, Li, D), mask (R, Li), t_scores (R, Li, 2).

@@ -147,6 +147,8 @@ SIGNATURES = {
     "stage_grp_pool_cls_bwd_tmp_bytes": (SZ, [LL, I, I]),
     "stage_grp_pool_cls_bwd": (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, F, P, P]),
     "stage_grp_pool_cls_bwd_s": (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, I, F, P, P]),
+    # the proposal decision on the device (csrc/proposals.hip): thd_host is a HOST array of two doubles {iou_thd, ce_prob_thd}
+    "stage_proposal_meta": (I, [P, I, I, P, I, P, P, P, P]),
     # evaluation head (csrc/eval_head.hip; G7 in csrc/groups.hip) and the prediction writer's span decoder
     "stage_eval_head_supported": (I, [I, I, I]),
     "stage_grp_eval_head_arena_bytes": (SZ, [LL, I, I]),

@@ -699,6 +699,27 @@ def topk_spans(x, k: int, is_prob: bool = False):
     return span, conf
 
 
+def proposal_meta(spans, k: int, iou_thd: float = 0.5, ce_prob_thd: float = 0.01, extra: int = 3):
+    """The decision of ``stage.proposal_rows`` on the device, at the fixed capacity Pmax = (k + 1) N: spans (3k + 3, N) as
+    ``gt_spans`` / ``gt_spans_topk`` leave them -> (meta (5 Pmax) int32 = src[Pmax] | win[2 Pmax] | inv[(k + 1) N] | tgt[Pmax],
+    count 0-d int32 = P, scale 0-d fp32 = N / P), all on the device.  Rows [0, P) are proposal_rows' rows, rows [P, Pmax) repeat
+    row 0 with target -100 and no inv entry (``stage.proposal_meta_host`` is the specification).  No read-back, no autograd node."""
+    spans = _chk(spans.detach(), "spans")
+    k = int(k)
+    if spans.dim() != 2 or spans.shape[0] != 3 * k + 3:
+        raise ValueError("proposal_meta: spans must be (3 k + 3, N), got %s for k = %d" % (tuple(spans.shape), k))
+    N = spans.shape[1]
+    slots = k + 1
+    meta = torch.empty(5 * slots * N, dtype=torch.int32, device=spans.device)
+    word = torch.empty(2, dtype=torch.int32, device=spans.device)         # count | scale, one allocation
+    count, scale = word[0], word[1].view(torch.float32)
+    thd = (ctypes.c_double * 2)(float(iou_thd), float(ce_prob_thd))
+    with torch.cuda.device(spans.device):
+        _rc(_lib.load().stage_proposal_meta(spans.data_ptr(), N, k, thd, int(extra), meta.data_ptr(), count.data_ptr(), scale.data_ptr(),
+                                            _stream()), "stage_proposal_meta")
+    return meta, count, scale
+
+
 def masked_max_raw(x, mask):
     """(R, L, D), (R, L) -> max (R, D), argmax (R, D) int32; no autograd node (the pooling group owns this gradient)."""
     x, mask = _chk(x.detach(), "x"), _chk(mask, "mask")

@@ -207,6 +207,47 @@ def proposal_rows(host, N: int, k: int = 1, iou_thd: float = 0.5, ce_prob_thd: f
     return src, wins, inv, tgt
 
 
+def proposal_meta_host(host, N: int, k: int = 1, iou_thd: float = 0.5, ce_prob_thd: float = 0.01, extra_span_length: int = 3):
+    """The specification of ``groups.proposal_meta`` (csrc/proposals.hip): ``proposal_rows`` laid out at the fixed capacity
+    Pmax = (k + 1) N.  Returns (meta, P): meta int32 (5 Pmax) = src[Pmax] | win[2 Pmax] | inv[(k + 1) N] | tgt[Pmax], the layout of
+    ``groups.pool_classifier`` with P = Pmax.  Rows [0, P) are proposal_rows' rows in its order; every row of [P, Pmax) repeats
+    row 0's src and window -- a real, finite row: an empty window would pool to -inf and put NaN into LayerNorm -- with target
+    -100, which the loss ignores, and no inv entry names it, so it reaches no gradient but exact zeros.  Pure Python / numpy."""
+    import numpy as np
+    src, wins, inv, tgt = proposal_rows(host, N, k, iou_thd, ce_prob_thd, extra_span_length)
+    P, Pmax = len(src), (k + 1) * N
+    if len(tgt) != P:
+        raise ValueError("proposal_meta_host: the span table has no answer row")
+    pad = Pmax - P
+    meta = np.asarray(src + [src[0]] * pad + wins + wins[:2] * pad + inv + tgt + [-100] * pad, dtype=np.int32)
+    return meta, P
+
+
+class ProposalInfo:
+    """``STAGE.last_proposals``: the classifier rows of the last training forward.  ``count`` (0-d int32) = P, the rows that carry
+    a target; ``scale`` (0-d fp32) = len(qids) / P, the factor of the reference's loss line (main.py:57-60); both on the device.
+    ``capacity`` = len(targets) of that forward; ``on_device``: the device decided (opt.device_proposals; count and scale then
+    never existed on the host) -- otherwise they are the host's numbers, uploaded when first asked for."""
+    __slots__ = ("capacity", "on_device", "_count", "_scale", "_host", "_device")
+
+    def __init__(self, capacity: int, on_device: bool, device, count=None, scale=None, host=None):
+        self.capacity, self.on_device, self._device = int(capacity), bool(on_device), device
+        self._count, self._scale, self._host = count, scale, host
+
+    @property
+    def count(self):
+        if self._count is None:
+            self._count = torch.tensor(self._host[1], dtype=torch.int32, device=self._device)
+        return self._count
+
+    @property
+    def scale(self):
+        if self._scale is None:
+            # float(n_examples) / len(targets) in double, narrowed once: what reference_loss hands to stage_train_loss
+            self._scale = torch.tensor(float(self._host[0]) / self._host[1], dtype=torch.float64).float().to(self._device)
+        return self._scale
+
+
 class _GatherExamples(torch.autograd.Function):
     """``x.index_select(0, src)`` for the proposal rows of get_proposals with a backward that sums in a FIXED order: the gradient of
     example n is the sum over its proposals inv[n, 0], inv[n, 1], ... in slot order.  index_select's own backward is an atomic
@@ -378,6 +419,13 @@ class STAGE(nn.Module):
         self._span_host = None      # pinned landing buffer of the per-step proposal spans (get_proposals)
         self._qas_host = None       # pinned landing buffer of the word ids in inference mode (box prediction's row table)
         self._meta_stage = None     # pinned staging of the per-step proposal bookkeeping (_proposals_grouped)
+        # opt.device_proposals (off by default): the training head decides its span proposals on the device (csrc/proposals.hip)
+        # instead of reading the span table back -- the step's one host wait goes, and with it the data-dependent row count:
+        # forward returns (max_num_proposal + 1) * N rows, the rows past the proposal count with target -100 (ignored by
+        # F.cross_entropy and reference_loss); the loss scale is ``last_proposals.scale``.  Taken where
+        # the grouped fp32 head runs (_proposals_grouped); elsewhere the read-back path runs and returns compact rows.
+        self.device_proposals = bool(_opt(opt, "device_proposals", False))
+        self.last_proposals: Optional[ProposalInfo] = None       # set by every training forward
         # counter-based dropout stream (csrc/common.h): seeded lazily from the seed of torch's default generator at the first
         # use (so torch.manual_seed() before training takes effect, as for the reference's nn.Dropout) and mixed with the
         # process rank (identical seeds on every data-parallel rank would drop the same units everywhere).  The stream
@@ -766,6 +814,9 @@ class STAGE(nn.Module):
                 return logits.view(-1, NA), targets, t_scores
         if (grouped_tail and self.add_local and self.training and gt_scores_fn is None and NA == self.num_a
                 and first.is_cuda):
+            if self.device_proposals:
+                logits, targets = self._proposals_on_device(first, mx_mask, t_scores, targets, ts_labels, extra_span_length)
+                return logits.view(-1, NA), targets, t_scores
             logits, targets = self._proposals_grouped(first, mx_mask, t_scores, targets, ts_labels, extra_span_length)
             return logits.view(-1, NA), targets, t_scores
         if self.add_local:
@@ -805,6 +856,28 @@ class STAGE(nn.Module):
         logits = groups.pool_classifier(x, m, glob, idx_g, meta, (N, NA, Li, D, P), self._p(), seeds,
                                         [cl.conv[0].weight, cl.conv[0].bias, cl.conv[2].weight, cl.conv[2].bias], slots=k + 1)
         return logits, meta[3 * P + (k + 1) * N:].long()
+
+    def _proposals_on_device(self, first, mx_mask, t_scores, targets, ts_labels, extra_span_length, iou_thd=0.5, ce_prob_thd=0.01):
+        """``_proposals_grouped`` without its read-back (opt.device_proposals): the span kernel, the proposal decision
+        (csrc/proposals.hip), the global max and the pooling + classifier group are queued back to back; the host never learns the
+        proposal count.  Pmax = (max_num_proposal + 1) N rows: rows [0, P) are the rows of the read-back path at the same indices
+        (same dropout words: the stream is keyed on the element index), rows [P, Pmax) repeat row 0 with target -100."""
+        N, NA, Li, D = first.shape
+        k = self.max_num_proposal
+        if k == 1:
+            spans = groups.gt_spans(t_scores, targets, ts_labels["st"], ts_labels["ed"])
+        else:
+            spans = groups.gt_spans_topk(t_scores, targets, ts_labels["st"], ts_labels["ed"], k)
+        meta, count, scale = groups.proposal_meta(spans, k, iou_thd, ce_prob_thd, extra_span_length)
+        x = first.reshape(N * NA, Li, D)
+        m = mx_mask.reshape(N * NA, Li)
+        glob, idx_g = groups.masked_max_raw(x, m)
+        Pmax = (k + 1) * N
+        cl = self.classifier
+        logits = groups.pool_classifier(x, m, glob, idx_g, meta, (N, NA, Li, D, Pmax), self._p(), self._seeds(1),
+                                        [cl.conv[0].weight, cl.conv[0].bias, cl.conv[2].weight, cl.conv[2].bias], slots=k + 1)
+        self.last_proposals = ProposalInfo(Pmax, True, first.device, count=count, scale=scale)
+        return logits, meta[4 * Pmax:].long()
 
     def get_ts_loss(self, temporal_scores, ts_labels, answer_indices, cand_offset: int = 0):
         """model/stage.py:539-555.  ``cand_offset``: global index of local candidate 0 when the candidates of an example
@@ -1273,10 +1346,14 @@ class STAGE(nn.Module):
                     self._att_stage = att_pairs.stage
         ctx_m = vid_mask if self.vfeat_flag else sub_mask       # the statement mask's context side (model/stage.py:386)
         factors = ((qas_mask != 0).any(-1), ctx_m.sum(-1) != 0)
+        self.last_proposals = None
         out, target, t_scores = self.classfier_head_multi_proposal(
             statement, statement_mask, batch.target, batch.ts_label, batch.ts_label_mask.float(),
             extra_span_length=self.extra_span_length, gt_scores_fn=gt_scores_fn, pool_mask_factors=factors, lay=lay, qa_mask=qas_mask)
         assert len(out) == len(target)
+        if self.training and self.last_proposals is None:
+            # the read-back path ran: the host knows the row count (the device words are made when somebody asks for them)
+            self.last_proposals = ProposalInfo(len(target), False, out.device, host=(N, len(target)))
         other_outputs["temporal_scores"] = t_scores
 
         if self.inference_mode:
