@@ -11,10 +11,10 @@ import torch
 import torch.nn.functional as F
 
 from conftest import rel_err
+from test_hip_topk_spans import _build, _head_inputs, _head_reference
 
 pytestmark = pytest.mark.gpu
 
-NEG = -1e10
 LO = np.float32(0.01)                        # below the double 0.01: rejected
 HI = np.nextafter(LO, np.float32(1))         # the next float up: kept
 
@@ -123,31 +123,6 @@ def test_nan_confidence_and_nan_start_make_the_rank_absent(hip_device):
     torch.cuda.synchronize()
 
 
-def _head_inputs():
-    """The construction of tests/test_hip_topk_spans.py: N = 4, NA = 5, Li = 12, D = 128.  At (prob_thd 0.01, IoU 0.5, k = 3) example 0
-    keeps none of its predicted spans, example 1 one, example 2 all three, example 3 is random with two masked trailing frames."""
-    g = torch.Generator().manual_seed(31)
-    N, NA, Li, D = 4, 5, 12, 128
-    t = torch.randn(N, NA, Li, 2, generator=g) * 2
-    targets = torch.tensor([1, 4, 0, 2])
-    lab_st, lab_ed = torch.tensor([8, 4, 3, 2]), torch.tensor([10, 7, 8, 6])
-
-    def peaked(main):
-        p = torch.full((Li,), (1.0 - sum(main.values())) / (Li - len(main)))
-        for i, v in main.items():
-            p[i] = v
-        return torch.log(p) + 0.01 * torch.randn(Li, generator=g)
-    t[0, 1, :, 0], t[0, 1, :, 1] = peaked({1: 0.9}), peaked({2: 0.6, 3: 0.3})
-    t[1, 4, :, 0], t[1, 4, :, 1] = peaked({4: 0.97}), peaked({7: 0.97})
-    t[2, 0, :, 0], t[2, 0, :, 1] = peaked({3: 0.5, 4: 0.3}), peaked({8: 0.6, 7: 0.3})
-    frame_mask = torch.ones(N, Li)
-    frame_mask[3, Li - 2:] = 0
-    t = t * frame_mask.view(N, 1, Li, 1) + (1 - frame_mask.view(N, 1, Li, 1)) * NEG
-    first = torch.randn(N, NA, Li, D, generator=g)
-    mx_mask = frame_mask.view(N, 1, Li, 1).expand(N, NA, Li, 1).clone()
-    return first, mx_mask, t, targets, dict(st=lab_st, ed=lab_ed)
-
-
 def test_from_real_scores(hip_device):
     """The table of gt_spans_topk itself, used as it is: the device rows equal proposal_rows on the read-back of that table."""
     from tvqaplus_amd import groups
@@ -179,27 +154,6 @@ def test_from_real_scores(hip_device):
 
 
 # ---- 2. the head ------------------------------------------------------------------------------------------------------------------
-def _head_reference(first, mx_mask, t, targets, ts, params, k, extra):
-    """fp64 autograd restatement from the oracle's functions (model/stage.py:408-438, 526-536), as tests/test_hip_topk_spans.py's."""
-    from oracle import stage_oracle as O
-    N, NA, Li, D = first.shape
-    ca = torch.softmax(t[torch.arange(N), targets].double(), dim=1)
-    pred = O.best_spans(ca[:, :, 0], ca[:, :, 1], top_n=k, prob_thd=0.01)
-    masked = O.mask_logits(first, mx_mask.double())
-    loc, glo, tgt = [], [], []
-    for n in range(N):
-        gt = (int(ts["st"][n]), int(ts["ed"][n]) + 1)
-        spans = [gt] + [(s, e + 1) for (s, e, _c) in pred[n] if O.temporal_iou((s, e + 1), gt) >= 0.5]
-        for sp in spans:
-            s, e = O.expand_span(sp, extra)
-            loc.append(masked[n, :, s:e].max(dim=1)[0])
-            glo.append(masked[n].max(dim=1)[0])
-            tgt.append(int(targets[n]))
-    pooled = torch.cat([torch.stack(loc), torch.stack(glo)], dim=-1)
-    y = F.layer_norm(pooled, (2 * D,), params[0], params[1], 1e-5)
-    return F.linear(y, params[2], params[3]).squeeze(2), tgt
-
-
 @pytest.mark.parametrize("p_drop", [0.0, 0.3])
 @pytest.mark.parametrize("k", [3, 1])
 def test_head_on_device_against_read_back_and_fp64(hip_device, k, p_drop):
@@ -260,7 +214,7 @@ def test_head_on_device_against_read_back_and_fp64(hip_device, k, p_drop):
     if p_drop == 0.0:
         f64 = first.double().requires_grad_()
         p64 = [p.detach().cpu().double().requires_grad_() for p in plist]
-        ref, ref_tgt = _head_reference(f64, mx_mask, t, targets, ts, p64, k, extra)
+        ref, ref_tgt, _ = _head_reference(f64, mx_mask, t, targets, ts, p64, k, extra)
         assert ref.shape[0] == P and d1[1][:P].tolist() == ref_tgt
         (ref * w_all[:P]).sum().backward()
         errs = dict(logits=rel_err(d1[0][:P], ref.detach()), d_first=rel_err(d1[2], f64.grad))
@@ -273,19 +227,6 @@ def test_head_on_device_against_read_back_and_fp64(hip_device, k, p_drop):
 
 # ---- 3. the whole model -----------------------------------------------------------------------------------------------------------
 SMALL = (dict(hsz=32, embedding_size=48, vfeat_size=40, add_local=True, dropout=0.2), dict(N=2, Li=5, Lr=7, Lw=9, Lqa=6, wd_size=48, vfeat_size=40))
-
-
-def _build(kw, seed=3):
-    from tvqaplus_amd.stage import STAGE
-    from tvqaplus_amd.synth import make_opt
-    torch.manual_seed(seed)
-    with contextlib.redirect_stdout(io.StringIO()):
-        model = STAGE(make_opt(**kw))
-    with torch.no_grad():
-        for p in model.parameters():
-            p.add_(0.05 * torch.randn_like(p))
-    model.use_ragged = False
-    return model
 
 
 def _step(model, batch, use_groups=True, backward=True):

@@ -192,11 +192,14 @@ def _head_reference(first, mx_mask, t, targets, ts, params, k, extra):
     return F.linear(y, params[2], params[3]).squeeze(2), tgt, counts
 
 
-@pytest.mark.parametrize("grouped", [True, False])
-def test_head_with_three_proposals_against_fp64(hip_device, grouped):
+@pytest.mark.parametrize("k", [3, 1])
+@pytest.mark.parametrize("route", ["grouped", "per-op", "per-op sharded"])
+def test_head_proposals_against_fp64(hip_device, route, k):
+    """``per-op sharded``: the span table from ``gt_scores_fn``'s rows (candidate-sharded batches, parallel.CandidateLayout.gt_scores)."""
     from tvqaplus_amd.stage import STAGE
     from tvqaplus_amd.synth import make_opt
-    k, extra = 3, 3
+    extra = 3
+    gt_scores_fn = (lambda t, tg: t[torch.arange(len(tg), device=tg.device), tg]) if route == "per-op sharded" else None
     torch.manual_seed(9)
     with contextlib.redirect_stdout(io.StringIO()):
         model = STAGE(make_opt(hsz=128, add_local=True, dropout=0.0, max_num_proposal=k)).to(hip_device).train()
@@ -209,7 +212,10 @@ def test_head_with_three_proposals_against_fp64(hip_device, grouped):
     f64 = first.double().requires_grad_()
     p64 = [p.detach().cpu().double().requires_grad_() for p in plist]
     ref, ref_tgt, counts = _head_reference(f64, mx_mask, t, targets, ts, p64, k, extra)
-    assert counts[:3] == [1, 2, 4] and max(counts) >= 3        # a stride-2 inverse table would lose rows of example 2
+    if k == 3:
+        assert counts[:3] == [1, 2, 4] and max(counts) >= 3    # a stride-2 inverse table would lose rows of example 2
+    else:
+        assert counts == [1, 2, 2, 1]                          # one example with a single row, two with a kept proposal
     w = torch.randn(ref.shape, generator=torch.Generator().manual_seed(4), dtype=torch.float64)
     (ref * w).sum().backward()
 
@@ -220,10 +226,11 @@ def test_head_with_three_proposals_against_fp64(hip_device, grouped):
         for p in plist:
             p.grad = None
         fd = dev(first).requires_grad_()
-        if grouped:
+        if route == "grouped":
             logits, tg = model._proposals_grouped(fd, dev(mx_mask), dev(t), dev(targets), tsd, extra)
         else:
-            pooled, tg = model.get_proposals(fd, dev(mx_mask), dev(t), dev(targets), tsd, extra_span_length=extra)
+            pooled, tg = model.get_proposals(fd, dev(mx_mask), dev(t), dev(targets), tsd, extra_span_length=extra,
+                                             gt_scores_fn=gt_scores_fn)
             logits, _ = model._linear_wrapper(pooled.reshape(-1, pooled.shape[-1]), cl)
         logits = logits.view(-1, 5)
         (logits * dev(w).float()).sum().backward()
@@ -234,7 +241,7 @@ def test_head_with_three_proposals_against_fp64(hip_device, grouped):
     errs = dict(logits=rel_err(a[0], ref.detach()), d_first=rel_err(a[2], f64.grad))
     for name, got, want in zip(("ln.w", "ln.b", "fc.w", "fc.b"), a[3], p64):
         errs[name] = rel_err(got, want.grad)
-    print("head k = 3 (%s): %s" % ("grouped" if grouped else "per-op", ", ".join("%s %.2e" % kv for kv in errs.items())))
+    print("head k = %d (%s): %s" % (k, route, ", ".join("%s %.2e" % kv for kv in errs.items())))
     for name, e in errs.items():
         assert e <= 2e-4, (name, e)
     # two identical steps are bit-equal (the per-op path sums an example's proposals in slot order, not by atomics)

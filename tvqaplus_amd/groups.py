@@ -738,7 +738,7 @@ class _PoolCls(torch.autograd.Function):
         first, mask, glob = _chk(first, "first"), _chk(mask, "mask"), _chk(glob, "glob")
         idx_g, meta = _chk(idx_g, "idx_g", torch.int32), _chk(meta, "meta", torch.int32)
         params = _params(params)
-        N, NA, Li, D, P = dims[:5]
+        N, NA, Li, D, P, _slots = dims
         lib = _lib.load()
         ab = _size("stage_grp_pool_cls_arena_bytes", P, NA, D)
         arena = _buf(ab, first.device)
@@ -746,7 +746,7 @@ class _PoolCls(torch.autograd.Function):
         _rc(lib.stage_grp_pool_cls_fwd(first.data_ptr(), mask.data_ptr(), glob.data_ptr(), meta.data_ptr(), _ptrs(params), logits.data_ptr(),
                                        arena.data_ptr(), ab, N, NA, Li, D, P, float(p), _u64(seeds), _stream()), "stage_grp_pool_cls_fwd")
         ctx.save_for_backward(first, mask, idx_g, meta, arena, *params)
-        ctx.cfg = ((N, NA, Li, D, P, int(dims[5]) if len(dims) > 5 else 2), float(p), tuple(seeds), ab)
+        ctx.cfg = (dims, float(p), tuple(seeds), ab)
         return logits
 
     @_on_device
@@ -759,14 +759,10 @@ class _PoolCls(torch.autograd.Function):
         d_first = torch.empty_like(first)
         tb = _size("stage_grp_pool_cls_bwd_tmp_bytes", P, NA, D)
         tmp = _buf(tb, first.device)
-        if slots == 2:
-            _rc(lib.stage_grp_pool_cls_bwd(d_logits.data_ptr(), mask.data_ptr(), idx_g.data_ptr(), meta.data_ptr(), _ptrs(params),
-                                           _ptrs(grads), d_first.data_ptr(), arena.data_ptr(), ab, tmp.data_ptr(), tb, N, NA, Li, D, P, p,
-                                           _u64(seeds), _stream()), "stage_grp_pool_cls_bwd")
-        else:
-            _rc(lib.stage_grp_pool_cls_bwd_s(d_logits.data_ptr(), mask.data_ptr(), idx_g.data_ptr(), meta.data_ptr(), _ptrs(params),
-                                             _ptrs(grads), d_first.data_ptr(), arena.data_ptr(), ab, tmp.data_ptr(), tb, N, NA, Li, D, P,
-                                             slots, p, _u64(seeds), _stream()), "stage_grp_pool_cls_bwd_s")
+        # slots == 2 selects the two-slot kernel on the C side: what stage_grp_pool_cls_bwd (still exported) forwards to
+        _rc(lib.stage_grp_pool_cls_bwd_s(d_logits.data_ptr(), mask.data_ptr(), idx_g.data_ptr(), meta.data_ptr(), _ptrs(params),
+                                         _ptrs(grads), d_first.data_ptr(), arena.data_ptr(), ab, tmp.data_ptr(), tb, N, NA, Li, D, P,
+                                         slots, p, _u64(seeds), _stream()), "stage_grp_pool_cls_bwd_s")
         return (d_first, None, None, None, None, None, None, None) + tuple(grads)
 
 
@@ -778,8 +774,7 @@ def pool_classifier(first, mask, glob, idx_g, meta, dims, p: float, seeds, param
     slots = int(slots)
     if not 1 <= slots <= _lib.STAGE_TOPK_MAX + 1:
         raise Unsupported("pool_classifier: slots = %d" % slots)
-    dims = tuple(dims)[:5]
-    return _PoolCls.apply(first, mask, glob, idx_g, meta, dims if slots == 2 else dims + (slots,), p, tuple(seeds), *params)
+    return _PoolCls.apply(first, mask, glob, idx_g, meta, tuple(dims)[:5] + (slots,), p, tuple(seeds), *params)
 
 
 class _TsLoss(torch.autograd.Function):

@@ -175,7 +175,7 @@ def reference_loss(outputs, targets, att_loss, temporal_loss, n_examples: int, a
 
 def proposal_rows(host, N: int, k: int = 1, iou_thd: float = 0.5, ce_prob_thd: float = 0.01, extra_span_length: int = 3):
     """The host half of get_proposals in training (model/stage.py:411-438; model/model_utils.py:37-89): which spans of every example
-    train the classifier.  ``host``: the read-back of ``groups.gt_spans`` / ``groups.gt_spans_topk`` as rows of Python floats -- rows
+    train the classifier.  ``host``: the read-back of ``STAGE._span_table`` as rows of Python floats -- rows
     3j, 3j + 1, 3j + 2 = start, end (inclusive), confidence of rank j < k, then the label's start, end (inclusive) and, if present,
     the answer index.  Per example, in order: the label's span, then the ranks with confidence >= ce_prob_thd whose IoU with the
     label's span (intersection / hull, end exclusive) is >= iou_thd; ranks the kernel left empty (start < 0) are skipped.  Returns
@@ -416,7 +416,7 @@ class STAGE(nn.Module):
         if sd not in ("fp32", "float32", "bf16", "bfloat16"):
             raise ValueError("opt.storage_dtype must be 'fp32' or 'bf16', got %r" % sd)
         self.storage = torch.bfloat16 if sd in ("bf16", "bfloat16") else torch.float32
-        self._span_host = None      # pinned landing buffer of the per-step proposal spans (get_proposals)
+        self._span_host = None      # pinned landing buffer of the per-step proposal spans (_read_spans)
         self._qas_host = None       # pinned landing buffer of the word ids in inference mode (box prediction's row table)
         self._meta_stage = None     # pinned staging of the per-step proposal bookkeeping (_proposals_grouped)
         # opt.device_proposals (off by default): the training head decides its span proposals on the device (csrc/proposals.hip)
@@ -639,75 +639,36 @@ class STAGE(nn.Module):
         conf, flat = prod.view(R, -1).max(dim=1)
         return flat // Li, flat % Li, conf
 
-    def get_proposals(self, max_statement, max_statement_mask, temporal_scores, targets, ts_labels,
-                      iou_thd=0.5, ce_prob_thd=0.01, extra_span_length=3, gt_scores_fn=None):
-        N, NA, Li, D = max_statement.shape
-        x = max_statement.reshape(N * NA, Li, D)
-        m = max_statement_mask.reshape(N * NA, Li)
-        if self.training and self.max_num_proposal > 1:
-            return self._get_proposals_topk(max_statement, max_statement_mask, temporal_scores, targets, ts_labels, iou_thd,
-                                            ce_prob_thd, extra_span_length, gt_scores_fn)
-        if self.training:
-            # ground-truth candidate's scores (:408-409); with the candidates of an example spread over a rank group they
-            # come from the rank that holds it (parallel.CandidateLayout.gt_scores)
+    def _span_table(self, temporal_scores, targets, ts_labels, gt_scores_fn=None, per_op=False):
+        """The span table of training, on the device (no gradient): rows 3j, 3j + 1, 3j + 2 = start, end (inclusive), confidence of
+        rank j < k = max_num_proposal of the ground-truth candidate (model/stage.py:408-418), then the label's start and end -- the
+        rows ``proposal_rows`` and ``groups.proposal_meta`` read.  The kernels append the answer index: (3k + 3, N).
+        ``per_op`` with k = 1: softmax + ``_best_span`` in torch, 5 rows -- the route for Li > 2048, which the span kernels decline.
+        ``gt_scores_fn``: candidate-sharded batches, the scores come from the rank that holds the candidate
+        (parallel.CandidateLayout.gt_scores)."""
+        k = self.max_num_proposal
+        lab_st, lab_ed = ts_labels["st"], ts_labels["ed"]
+        if gt_scores_fn is not None or (per_op and k == 1):
             gt = (gt_scores_fn(temporal_scores, targets) if gt_scores_fn is not None
-                  else temporal_scores[torch.arange(N, device=targets.device), targets])
-            ca = F.softmax(gt.detach(), dim=1)
-            st, ed, conf = self._best_span(ca[:, :, 0], ca[:, :, 1])
-            # one small D2H copy per step: the number of proposals (N_new) is data dependent by construction.  It is
-            # requested BEFORE the global masked max is queued and awaited through an event: the host resumes as soon as the
-            # 5 x N floats have arrived and issues the proposal kernels while that 0.1 ms kernel still runs.
-            dev_spans = torch.stack([st.float(), ed.float(), conf, ts_labels["st"].float(), ts_labels["ed"].float()])
-            if dev_spans.is_cuda:
-                if self._span_host is None or self._span_host.shape != dev_spans.shape:
-                    self._span_host = torch.empty(dev_spans.shape, dtype=torch.float32, pin_memory=True)
-                with torch.cuda.device(dev_spans.device):    # the model may live on a device that is not the current one
-                    self._span_host.copy_(dev_spans, non_blocking=True)
-                    arrived = torch.cuda.Event()
-                    arrived.record(torch.cuda.current_stream(dev_spans.device))
-                    glob = ops.masked_max(x, m)                                   # (N*5, D)
-                    arrived.synchronize()
-                host = self._span_host.tolist()
-            else:   # CPU tensors only reach this point in host-logic tests
-                glob = ops.masked_max(x, m)
-                host = dev_spans.tolist()
-            src, wins = [], []
-            for n in range(N):
-                gs, ge = int(host[3][n]), int(host[4][n]) + 1
-                spans = [(gs, ge)]
-                if host[2][n] >= ce_prob_thd:
-                    ps, pe = int(host[0][n]), int(host[1][n]) + 1
-                    inter = max(0, min(pe, ge) - max(ps, gs))
-                    union = max(pe, ge) - min(ps, gs)
-                    if union != 0 and inter / union >= iou_thd:
-                        spans.append((ps, pe))
-                for (s, e) in spans:
-                    src.append(n)
-                    wins.append((max(0, s - extra_span_length), e + extra_span_length))
-            src_t = torch.tensor(src, device=x.device, dtype=torch.long)
-            win_t = torch.tensor(wins, device=x.device, dtype=torch.int32)       # (N_new, 2)
-            # index_select (backward: one index_add; at most two contributions per slot here -- max_num_proposal = 1 -- so the
-            # order cannot matter; more proposals per example: _get_proposals_topk sums in a fixed order)
-            # instead of advanced indexing (backward: sort-based index_put, five small kernels each)
-            xg = max_statement.index_select(0, src_t).reshape(-1, Li, D)          # (N_new*5, Li, D)
-            mg = max_statement_mask.reshape(N, NA, Li).index_select(0, src_t).reshape(-1, Li)
-            wg = win_t.unsqueeze(1).expand(-1, NA, -1).reshape(-1, 2).contiguous()
-            loc = ops.masked_max(xg, mg, wg).view(-1, NA, D)
-            pooled = torch.cat([loc, glob.view(N, NA, D).index_select(0, src_t)], dim=-1)   # (N_new, 5, 2D)
-            return pooled, targets.index_select(0, src_t)
-        glob = ops.masked_max(x, m)                                               # (N*5, D)
-        ts = F.softmax(temporal_scores, dim=2).view(N * NA, Li, 2)
-        st, ed, _ = self._best_span(ts[:, :, 0], ts[:, :, 1])
-        win = torch.stack([(st - extra_span_length).clamp(min=0), ed + 1 + extra_span_length], dim=1).int().contiguous()
-        loc = ops.masked_max(x, m, win)
-        return torch.cat([loc, glob], dim=-1).view(N, NA, 2 * D), targets
+                  else temporal_scores[torch.arange(len(targets), device=targets.device), targets]).detach()
+            if k == 1:
+                ca = F.softmax(gt, dim=1)
+                st, ed, conf = self._best_span(ca[:, :, 0], ca[:, :, 1])
+                return torch.stack([st.float(), ed.float(), conf, lab_st.float(), lab_ed.float()])
+            span, conf = groups.topk_spans(gt.float(), k)
+            ranks = torch.cat([span.float(), conf.unsqueeze(2)], dim=2).reshape(len(targets), 3 * k).t()
+            return torch.cat([ranks, torch.stack([lab_st.float(), lab_ed.float(), targets.float()])]).contiguous()
+        if k == 1:
+            return groups.gt_spans(temporal_scores, targets, lab_st, lab_ed)          # 20.6 us against 30.2 us (docs/findings.md 70)
+        return groups.gt_spans_topk(temporal_scores.float(), targets, lab_st, lab_ed, k)
 
     def _read_spans(self, spans, then):
         """One copy of the span table to the pinned landing buffer; ``then()`` is queued behind it and runs while the host waits for
-        the event.  Returns (rows of Python floats, then())."""
+        the event.  Returns (rows of Python floats, then()).  The one D2H copy of a step: the number of proposals is data dependent
+        by construction; the host resumes as soon as the few floats per example have arrived."""
         if self._span_host is None or self._span_host.shape != spans.shape:
             self._span_host = torch.empty(spans.shape, dtype=torch.float32, pin_memory=True)
-        with torch.cuda.device(spans.device):
+        with torch.cuda.device(spans.device):            # the model may live on a device that is not the current one
             self._span_host.copy_(spans, non_blocking=True)
             arrived = torch.cuda.Event()
             arrived.record(torch.cuda.current_stream(spans.device))
@@ -715,31 +676,42 @@ class STAGE(nn.Module):
             arrived.synchronize()
         return self._span_host.tolist(), res
 
-    def _get_proposals_topk(self, max_statement, max_statement_mask, temporal_scores, targets, ts_labels, iou_thd, ce_prob_thd,
-                            extra_span_length, gt_scores_fn):
-        """get_proposals in training with max_num_proposal = k > 1 on the per-op path: the k best spans of the ground-truth candidate
-        from the top-K kernel, one read-back of (3k + 3) N floats, ``proposal_rows`` on the host, then the pooling ops."""
+    @staticmethod
+    def _example_gather(src_t, inv, N: int):
+        """v -> v.index_select(0, src_t), the proposal rows of (N, ...) example rows, with a backward fit for ``inv`` (proposal_rows').
+        At most two slots per example (max_num_proposal = 1): plain index_select -- its backward is one index_add, and with at most
+        two contributions per example the order cannot matter (advanced indexing instead: a sort-based index_put, five small kernels
+        each).  More slots: ``_GatherExamples``, which sums in slot order."""
+        if len(inv) <= 2 * N:
+            return lambda v: v.index_select(0, src_t)
+        inv_t = torch.tensor(inv, device=src_t.device, dtype=torch.long).view(N, -1)
+        return lambda v: _GatherExamples.apply(v, src_t, inv_t)
+
+    def get_proposals(self, max_statement, max_statement_mask, temporal_scores, targets, ts_labels,
+                      iou_thd=0.5, ce_prob_thd=0.01, extra_span_length=3, gt_scores_fn=None):
         N, NA, Li, D = max_statement.shape
-        k = self.max_num_proposal
         x = max_statement.reshape(N * NA, Li, D)
         m = max_statement_mask.reshape(N * NA, Li)
-        if gt_scores_fn is not None:
-            # candidate-sharded batches: the scores come from the rank that holds the candidate (parallel.CandidateLayout.gt_scores)
-            span, conf = groups.topk_spans(gt_scores_fn(temporal_scores, targets).detach().float(), k)
-            ranks = torch.cat([span.float(), conf.unsqueeze(2)], dim=2).reshape(N, 3 * k).t()
-            dev_spans = torch.cat([ranks, torch.stack([ts_labels["st"].float(), ts_labels["ed"].float(), targets.float()])]).contiguous()
-        else:
-            dev_spans = groups.gt_spans_topk(temporal_scores.float(), targets, ts_labels["st"], ts_labels["ed"], k)
-        host, glob = self._read_spans(dev_spans, lambda: ops.masked_max(x, m))
-        src, wins, inv, _ = proposal_rows(host, N, k, iou_thd, ce_prob_thd, extra_span_length)
-        src_t = torch.tensor(src, device=x.device, dtype=torch.long)
-        inv_t = torch.tensor(inv, device=x.device, dtype=torch.long).view(N, k + 1)
-        wg = torch.tensor(wins, device=x.device, dtype=torch.int32).view(-1, 1, 2).expand(-1, NA, -1).reshape(-1, 2).contiguous()
-        xg = _GatherExamples.apply(max_statement, src_t, inv_t).reshape(-1, Li, D)          # (N_new*5, Li, D)
-        mg = max_statement_mask.reshape(N, NA, Li).index_select(0, src_t).reshape(-1, Li)
-        loc = ops.masked_max(xg, mg, wg).view(-1, NA, D)
-        pooled = torch.cat([loc, _GatherExamples.apply(glob.view(N, NA, D), src_t, inv_t)], dim=-1)   # (N_new, 5, 2D)
-        return pooled, targets.index_select(0, src_t)
+        if self.training:
+            # the per-op path: span table, one read-back with the global max (N*5, D) queued behind it, ``proposal_rows`` on the
+            # host, then the pooling ops
+            spans = self._span_table(temporal_scores, targets, ts_labels, gt_scores_fn, per_op=True)
+            host, glob = self._read_spans(spans, lambda: ops.masked_max(x, m))
+            src, wins, inv, _ = proposal_rows(host, N, self.max_num_proposal, iou_thd, ce_prob_thd, extra_span_length)
+            src_t = torch.tensor(src, device=x.device, dtype=torch.long)
+            gather = self._example_gather(src_t, inv, N)
+            wg = torch.tensor(wins, device=x.device, dtype=torch.int32).view(-1, 1, 2).expand(-1, NA, -1).reshape(-1, 2).contiguous()
+            xg = gather(max_statement).reshape(-1, Li, D)                                   # (N_new*5, Li, D)
+            mg = max_statement_mask.reshape(N, NA, Li).index_select(0, src_t).reshape(-1, Li)
+            loc = ops.masked_max(xg, mg, wg).view(-1, NA, D)
+            pooled = torch.cat([loc, gather(glob.view(N, NA, D))], dim=-1)                  # (N_new, 5, 2D)
+            return pooled, targets.index_select(0, src_t)
+        glob = ops.masked_max(x, m)                                               # (N*5, D)
+        ts = F.softmax(temporal_scores, dim=2).view(N * NA, Li, 2)
+        st, ed, _ = self._best_span(ts[:, :, 0], ts[:, :, 1])
+        win = torch.stack([(st - extra_span_length).clamp(min=0), ed + 1 + extra_span_length], dim=1).int().contiguous()
+        loc = ops.masked_max(x, m, win)
+        return torch.cat([loc, glob], dim=-1).view(N, NA, 2 * D), targets
 
     def _linear_wrapper(self, x, lw: _LinearWrapperParams, res=None):
         y, s = self._ln(x, lw.conv[0], drop=True, res=res)
@@ -827,57 +799,52 @@ class STAGE(nn.Module):
         logits, _ = self._linear_wrapper(pooled.reshape(-1, pooled.shape[-1]), self.classifier)
         return logits.view(-1, NA).float(), targets, t_scores
 
+    def _pool_classify(self, first, mx_mask, decide):
+        """What the two grouped routes share behind the span table: the global max, then ONE pooling + classifier group
+        (csrc/groups.hip, G6) over P rows.  ``decide(global_max)`` -> (meta, P, global_max()): it names the rows (meta = src[P] |
+        win[2 P] | inv[slots N] | tgt[P], device int32) and calls ``global_max`` where that launch is to sit in the queue.  Returns
+        (logits (P * NA, 1), the rows' targets (P) int64)."""
+        N, NA, Li, D = first.shape
+        x = first.reshape(N * NA, Li, D)
+        m = mx_mask.reshape(N * NA, Li)
+        meta, P, (glob, idx_g) = decide(lambda: groups.masked_max_raw(x, m))
+        cl = self.classifier
+        slots = self.max_num_proposal + 1
+        logits = groups.pool_classifier(x, m, glob, idx_g, meta, (N, NA, Li, D, P), self._p(), self._seeds(1),
+                                        [cl.conv[0].weight, cl.conv[0].bias, cl.conv[2].weight, cl.conv[2].bias], slots=slots)
+        return logits, meta[3 * P + slots * N:].long()
+
     def _proposals_grouped(self, first, mx_mask, t_scores, targets, ts_labels, extra_span_length,
                            iou_thd=0.5, ce_prob_thd=0.01):
         """get_proposals (training, model/stage.py:406-438) + classifier (:536) on the K-group path: one span kernel before the
-        per-step read-back, ONE pooling + classifier group after it (csrc/groups.hip, G6), the proposal bookkeeping
-        (source example, frame window, inverse map) uploaded as one int32 tensor through pinned staging."""
+        per-step read-back, ONE pooling + classifier group after it, the proposal bookkeeping (source example, frame window,
+        inverse map) uploaded as one int32 tensor through pinned staging."""
         from .att_host import PinnedStage
-        N, NA, Li, D = first.shape
-        dev = first.device
-        k = self.max_num_proposal
-        if k == 1:
-            spans = groups.gt_spans(t_scores, targets, ts_labels["st"], ts_labels["ed"])     # (6, N) device floats
-        else:
-            spans = groups.gt_spans_topk(t_scores, targets, ts_labels["st"], ts_labels["ed"], k)      # (3k + 3, N)
-        x = first.reshape(N * NA, Li, D)
-        m = mx_mask.reshape(N * NA, Li)
-        # the global max is queued behind the copy: it runs while the host reads the spans
-        host, (glob, idx_g) = self._read_spans(spans, lambda: groups.masked_max_raw(x, m))
-        # the repeated targets travel with the bookkeeping (ATen's index_select switches kernels at 16 indices: the first step
-        # with a 17th proposal paid ~9 ms of lazy kernel loading inside the training loop)
-        src, wins, inv, tgt = proposal_rows(host, N, k, iou_thd, ce_prob_thd, extra_span_length)
-        P = len(src)
-        if self._meta_stage is None:
-            self._meta_stage = PinnedStage()
-        meta = self._meta_stage.upload(torch.tensor(src + wins + inv + tgt, dtype=torch.int32), dev)
-        cl = self.classifier
-        seeds = self._seeds(1)
-        logits = groups.pool_classifier(x, m, glob, idx_g, meta, (N, NA, Li, D, P), self._p(), seeds,
-                                        [cl.conv[0].weight, cl.conv[0].bias, cl.conv[2].weight, cl.conv[2].bias], slots=k + 1)
-        return logits, meta[3 * P + (k + 1) * N:].long()
+        N = first.shape[0]
+        spans = self._span_table(t_scores, targets, ts_labels)
+
+        def decide(global_max):
+            # the global max is queued behind the copy: it runs while the host reads the spans
+            host, res = self._read_spans(spans, global_max)
+            # the repeated targets travel with the bookkeeping (ATen's index_select switches kernels at 16 indices: the first step
+            # with a 17th proposal paid ~9 ms of lazy kernel loading inside the training loop)
+            src, wins, inv, tgt = proposal_rows(host, N, self.max_num_proposal, iou_thd, ce_prob_thd, extra_span_length)
+            if self._meta_stage is None:
+                self._meta_stage = PinnedStage()
+            return self._meta_stage.upload(torch.tensor(src + wins + inv + tgt, dtype=torch.int32), first.device), len(src), res
+        return self._pool_classify(first, mx_mask, decide)
 
     def _proposals_on_device(self, first, mx_mask, t_scores, targets, ts_labels, extra_span_length, iou_thd=0.5, ce_prob_thd=0.01):
         """``_proposals_grouped`` without its read-back (opt.device_proposals): the span kernel, the proposal decision
         (csrc/proposals.hip), the global max and the pooling + classifier group are queued back to back; the host never learns the
         proposal count.  Pmax = (max_num_proposal + 1) N rows: rows [0, P) are the rows of the read-back path at the same indices
         (same dropout words: the stream is keyed on the element index), rows [P, Pmax) repeat row 0 with target -100."""
-        N, NA, Li, D = first.shape
         k = self.max_num_proposal
-        if k == 1:
-            spans = groups.gt_spans(t_scores, targets, ts_labels["st"], ts_labels["ed"])
-        else:
-            spans = groups.gt_spans_topk(t_scores, targets, ts_labels["st"], ts_labels["ed"], k)
+        Pmax = (k + 1) * first.shape[0]
+        spans = self._span_table(t_scores, targets, ts_labels)
         meta, count, scale = groups.proposal_meta(spans, k, iou_thd, ce_prob_thd, extra_span_length)
-        x = first.reshape(N * NA, Li, D)
-        m = mx_mask.reshape(N * NA, Li)
-        glob, idx_g = groups.masked_max_raw(x, m)
-        Pmax = (k + 1) * N
-        cl = self.classifier
-        logits = groups.pool_classifier(x, m, glob, idx_g, meta, (N, NA, Li, D, Pmax), self._p(), self._seeds(1),
-                                        [cl.conv[0].weight, cl.conv[0].bias, cl.conv[2].weight, cl.conv[2].bias], slots=k + 1)
         self.last_proposals = ProposalInfo(Pmax, True, first.device, count=count, scale=scale)
-        return logits, meta[4 * Pmax:].long()
+        return self._pool_classify(first, mx_mask, lambda global_max: (meta, Pmax, global_max()))
 
     def get_ts_loss(self, temporal_scores, ts_labels, answer_indices, cand_offset: int = 0):
         """model/stage.py:539-555.  ``cand_offset``: global index of local candidate 0 when the candidates of an example
