@@ -759,6 +759,45 @@ int stage_train_loss_meter(const float* logits, const long long* targets, const 
 int stage_meter_spans(void* meter, const float* answer, const float* t_prob, const long long* targets, const double* gt,
                       const double* thd_host, int N, int NA, int Li, int* rows_out, void* stream);
 
+/* ---- Grounding meter (eval/eval_tvqa_plus.py:94-146 + eval/maskrcnn_voc/voc_eval.py as tvqaplus_amd/evaluation.py restates them:
+ *      load_predictions :309-329, detection_map :225-282, _pairwise_iou :199-207) ---------------------------------------------------
+ * The fourth validation metric next to the run meter's three: the detection records of the grounding mAP, appended to ONE caller-owned
+ * device buffer by ONE launch per validation batch (csrc/grounding.hip; tvqaplus_amd/grounding.py: GroundingMeter), one wavefront per
+ * task.  The AP is a host-side sort over the records (evaluation.average_precision).  A task is one (example, annotated image, label)
+ * triple of the GROUND-TRUTH answer; `tasks` (T, 8) int64 ON THE DEVICE, one row per task:
+ *   0 word_off    offset of the statement's Lqa word ids in `words` (qas[b, answer, 0])
+ *   1 score_off   offset of scores[b, answer, frame, 0, 0] in `scores`: row w of the task is scores[score_off + w * Lr .. + Lr)
+ *   2 label       the word id, 0 .. 2^31 - 1
+ *   3 box_first   first region box of the image in `region_boxes`        4 n_boxes  their number (region r < n_boxes has a box)
+ *   5 gt_first    first ground-truth box of (image, label) in `gt_boxes`  6 n_gt     their number, >= 1
+ *   7 spare (0)
+ * region_boxes (n_region_boxes, 4), gt_boxes (n_gt_boxes, 4): float32 x1 y1 x2 y2 (finite), on the device.
+ * Per task (load_predictions + the inner loop of detection_map): the positions w (ascending) with words[word_off + w] == label (the
+ * comparison runs here, on the device word ids); of each such row the regions r with score >= thd (fp32; a NaN is never kept:
+ * stage_att_predict's rule); these detections in descending score order (equal scores: lower w, then lower r) each take the FIRST
+ * ground-truth box of the largest IoU -- _pairwise_iou on boxes whose far edges were incremented by 1, the same fp32 operations in the
+ * same order, compiled without contraction -- and match when that IoU is not below iou_thd and the box is not taken yet.
+ *
+ * The buffer is caller-owned, 8-byte aligned, stage_grounding_bytes(capacity) bytes:
+ *   byte  0  unsigned long long c[8]   0 cursor (records reserved; the first min(cursor, capacity) slots are written)
+ *                                      1 dropped (records that did not fit)  2 tasks  3 detections (of the tasks that emitted)
+ *                                      4 overflow  5 bad  6..7 reserved
+ *   byte 64  capacity records of 8 bytes: int32 (bits 0-30 the label, bit 31 the match), then the fp32 score.  Order across tasks:
+ *            unspecified (one atomic add on the cursor per task; the records are written with plain vector stores).
+ * A task writes nothing and is counted in `bad` when its row fails a bound -- label outside 0 .. 2^31 - 1, word_off + Lqa > n_words,
+ * a score row outside n_scores, box_first + n_boxes > n_region_boxes, n_gt < 1 or gt_first + n_gt > n_gt_boxes, any of them
+ * negative -- or when it has a kept region r >= n_boxes; in `overflow` when the label holds more than 8 positions or n_gt > 32
+ * (table bounds are judged first, then the limits, then the rows).  No read is made through an unchecked offset.
+ * stage_grounding_supported: 1 for 1 <= Lqa <= 64 and 1 <= Lr <= 64 (needs no GPU); stage_grounding_bytes needs no GPU (0 for
+ * capacity < 0).  stage_grounding_reset: asynchronous zero fill.  stage_grounding_update: STAGE_ERR_SHAPE before any launch for an
+ * unsupported Lqa / Lr, a NULL or misaligned buffer or table, a negative size; T == 0 launches nothing. */
+int stage_grounding_supported(int Lqa, int Lr);
+size_t stage_grounding_bytes(long long capacity);
+int stage_grounding_reset(void* buf, long long capacity, void* stream);
+int stage_grounding_update(void* buf, long long capacity, const float* scores, long long n_scores, const long long* words,
+                           long long n_words, const long long* tasks, int T, const float* region_boxes, long long n_region_boxes,
+                           const float* gt_boxes, long long n_gt_boxes, int Lqa, int Lr, float thd, float iou_thd, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ Layout (only what the path needs):
 * ``packed.py``    context features without their padding (``PackedFeatures``): the collate, the host specification of the unpad
 * ``prefetch.py``  pinned double-buffered host->HBM batch feed
 * ``evaluation.py``span selection, prediction writer and the reference's temporal / grounding metrics
+* ``grounding.py`` ``GroundingMeter``: the grounding mAP of a validation pass kept on the device (``csrc/grounding.hip``)
 * ``synth.py``     synthetic batches of the BASELINE.json shapes
 
 Nothing here imports ``oracle/`` (test infrastructure).

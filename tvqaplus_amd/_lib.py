@@ -211,6 +211,11 @@ SIGNATURES = {
     "stage_meter_update": (I, [P, LL, P, P, I, I, P, P, P, P, F, F, P, P]),
     "stage_train_loss_meter": (I, [P, P, P, P, P, F, F, F, P, P, I, I, P, P, LL]),
     "stage_meter_spans": (I, [P, P, P, P, P, P, I, I, I, P, P]),
+    # grounding meter (csrc/grounding.hip; tvqaplus_amd/grounding.py): the detection records of the grounding mAP in one device buffer
+    "stage_grounding_supported": (I, [I, I]),
+    "stage_grounding_bytes": (SZ, [LL]),
+    "stage_grounding_reset": (I, [P, LL, P]),
+    "stage_grounding_update": (I, [P, LL, P, LL, P, LL, P, I, P, LL, P, LL, I, I, F, F, P]),
 }
 
 ABI_VERSION = 5    # include/stage_hip.h: STAGE_HIP_ABI_VERSION (tests/test_abi.py holds the two together)

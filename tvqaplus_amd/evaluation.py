@@ -264,22 +264,30 @@ def detection_map(pred_by_image: Mapping[str, list], gt_by_image: Mapping[str, l
     idx2word = {i: w for w, i in w2i.items()}
     for l in np.unique(gt_all.astype(int)):
         n_pos = int(np.sum(gt_all.astype(int) == l))
-        sc, mt = np.array(scores[l]), np.array(matches[l], dtype=np.int8)
-        mt = mt[sc.argsort()[::-1]]
-        tp, fp = np.cumsum(mt == 1), np.cumsum(mt == 0)
-        with np.errstate(divide="ignore", invalid="ignore"):
-            prec = tp / (fp + tp)
-        rec = tp / n_pos
-        mpre = np.concatenate(([0], np.nan_to_num(prec), [0]))
-        mrec = np.concatenate(([0], rec, [1]))
-        mpre = np.maximum.accumulate(mpre[::-1])[::-1]
-        step = np.where(mrec[1:] != mrec[:-1])[0]
-        ap = float(np.sum((mrec[step + 1] - mrec[step]) * mpre[step + 1]))
-        aps.append(ap)
-        per_class[idx2word[int(l)]] = {"ap": ap, "class_id": int(l), "label": idx2word[int(l)], "precisions": prec.tolist(),
-                                      "recalls": rec.tolist(), "n_tp": int(np.sum(mt == 1)), "n_fp": int(np.sum(mt == 0)),
-                                      "n_positives": n_pos}
+        entry = average_precision(scores[l], matches[l], n_pos)
+        aps.append(entry["ap"])
+        entry.update(class_id=int(l), label=idx2word[int(l)])
+        per_class[idx2word[int(l)]] = entry
     return {"metrics_per_class": per_class, "overall_map": float(np.nanmean(aps)) if aps else float("nan")}
+
+
+def average_precision(scores: Sequence[float], matches: Sequence[int], n_pos: int) -> Dict[str, object]:
+    """The per-class tail of ``detection_map`` (and of ``grounding.GroundingState.metrics``): the detections of one class -- their
+    scores and 0 / 1 matches, in any order -- and its number of ground-truth boxes -> ``ap`` (area under the monotone precision
+    envelope), ``precisions``, ``recalls``, ``n_tp``, ``n_fp``, ``n_positives``."""
+    sc, mt = np.array(scores, dtype=np.float64), np.array(matches, dtype=np.int8)
+    mt = mt[sc.argsort()[::-1]]
+    tp, fp = np.cumsum(mt == 1), np.cumsum(mt == 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        prec = tp / (fp + tp)
+    rec = tp / n_pos
+    mpre = np.concatenate(([0], np.nan_to_num(prec), [0]))
+    mrec = np.concatenate(([0], rec, [1]))
+    mpre = np.maximum.accumulate(mpre[::-1])[::-1]
+    step = np.where(mrec[1:] != mrec[:-1])[0]
+    ap = float(np.sum((mrec[step + 1] - mrec[step]) * mpre[step + 1]))
+    return {"ap": ap, "precisions": prec.tolist(), "recalls": rec.tolist(), "n_tp": int(np.sum(mt == 1)), "n_fp": int(np.sum(mt == 0)),
+            "n_positives": int(n_pos)}
 
 
 # ---------------------------------------------------------------------------------------------------------------
