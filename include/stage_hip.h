@@ -27,7 +27,7 @@ extern "C" {
 #define STAGE_ERR_WORKSPACE (-2)  /* workspace too small */
 
 /* ---- library info -------------------------------------------------------------------------------------------- */
-#define STAGE_HIP_ABI_VERSION 5   /* what stage_hip_abi_version() of a matching library returns; bumped when an existing symbol's signature or meaning changes (added symbols keep it) */
+#define STAGE_HIP_ABI_VERSION 6   /* what stage_hip_abi_version() of a matching library returns; bumped when an existing symbol's signature or meaning changes (added symbols keep it) */
 int stage_hip_abi_version(void);
 const char* stage_hip_error_string(int code);
 /* Measurement helpers (bench.py; no reference counterpart): events for hosts without a HIP binding, and a one-shot hook that makes the
@@ -71,16 +71,11 @@ int stage_str_attn_bwd_fused(const float* dA, const float* dS_raw_ext, const flo
  * D = 256, 512 subtitle words per frame): the same StructuredAttention for ANY Lr (16-region blocks, two-pass softmax) and
  * D in {16, 32, 64, 128, 256}.  storage_bf16 != 0: Cn, Q, Qn, A, dA are bf16 (masks, scores, S maps and the gradients
  * dQraw / dQn / dCn stay fp32; every product accumulates in fp32).  Qn = normalised (+dropped) Q in storage precision.
- * Backward: A is the forward output (the softmax backward's row term <P, dP> equals <dA, A>); dS_ws is an (N,NA,Li,Lqa,Lr)
- * fp32 scratch that receives the gradient wrt the raw scores; ws from stage_str_attn_long_bwd_ws_bytes.              */
+ * Backward (below): A is the forward output (the softmax backward's row term <P, dP> equals <dA, A>); dS_ws is an
+ * (N,NA,Li,Lqa,Lr) fp32 scratch that receives the gradient wrt the raw scores.                                        */
 int stage_str_attn_long_fwd(const void* Cn, const void* Q, const void* Qn, const float* c_mask, const float* q_mask, void* A,
                             float* S_raw, float* S_norm, int N, int NA, int Li, int Lqa, int Lr, int D, float scale,
                             int storage_bf16, void* stream);
-size_t stage_str_attn_long_bwd_ws_bytes(int N, int NA, int Lqa, int D);
-int stage_str_attn_long_bwd(const void* dA, const void* A, const float* dS_raw_ext, const void* Cn, const void* Q,
-                            const void* Qn, const float* S_norm, float* dS_ws, float* dQraw, float* dQn, float* dCn, int N,
-                            int NA, int Li, int Lqa, int Lr, int D, float scale, int storage_bf16, void* ws, size_t ws_bytes,
-                            void* stream);
 
 /* The backward with the region mask at hand (round 4): region blocks behind a frame's last valid region are skipped -- there S_ = 0,
  * so dS, their share of dCn and the dQ rows are exact zeros (model/context_query_attention.py:58-61: masked scores are cos - 1e10) --
@@ -188,7 +183,6 @@ int stage_gemm_tn_mask(const float* dY, const unsigned* gate_mask, const float* 
                        int N, int K, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- encoder block pieces (model/encoder.py:35-44, model/position_encoding.py:38-43, model/cnn.py:23-26,44) ---- */
-int stage_add_pe(const float* x, const float* pe /*(>=L, D)*/, float* y, long long M, int L, int D, void* stream);
 int stage_dwconv_fwd(const float* in, const float* w /*(D,1,k)*/, const float* bias, float* out, long long M, int L,
                      int D, int k, void* stream);
 size_t stage_dwconv_bwd_ws_bytes(int D, int k);
@@ -359,16 +353,27 @@ int stage_cat3_bwd_dw(const float* dy, const unsigned* relu_mask, const float* W
  * pointers in the order each group documents; `seeds` = host array, one entry per dropout site in forward order.
  * STAGE_ERR_SHAPE is returned before anything is launched when a group does not take the shape (use the per-op entry points). */
 /* G1 input MLP (model/stage.py:350-362, :85-91, :98-104, :115-120; l2 != 0: F.normalize of :256 first):
- * [l2norm] -> LN(K0)+drop -> Linear(K0->H)+ReLU -> LN(H)+drop -> Linear(H->D)+ReLU -> LN(D).  x (M, K0) -> out (M, D).
- * params / grads: g0 b0 W1 c1 g1 b1 W2 c2 g2 b2; seeds[2].  The features receive no gradient.                            */
-size_t stage_grp_input_mlp_arena_bytes(long long M, int K0, int H, int D, int l2);
-int stage_grp_input_mlp_fwd(const float* x, const float* const* params, float* out, void* arena, size_t arena_bytes, int* flags,
-                            long long M, int K0, int H, int D, int l2, float p_drop, const unsigned long long* seeds,
-                            void* stream);
+ * [l2norm] -> LN(K0)+drop -> Linear(K0->H)+ReLU -> LN(H)+drop -> Linear(H->D)+ReLU -> LN(D).  M rows of x -> out (M, D).
+ * params / grads: g0 b0 W1 c1 g1 b1 W2 c2 g2 b2; seeds[2]; flags[2].  The features receive no gradient.
+ * One entry point per direction; the forms differ in the first stage only:
+ *   dtype     STAGE_DT_F32: x holds fp32 rows.  STAGE_DT_F16 / STAGE_DT_BF16: x holds half-precision rows that the first stage reads
+ *             in place (stage_feat16_ln_* below) -- no fp32 image of the features and, with l2, no normalised image is written.
+ *   src_rows  NULL: the rows are rows 0..M of x.  Otherwise (M) int32, row r reads x[src_rows[r]]: the live rows of a padded ragged
+ *             context stream (stage_rag_ctx_rows) or the rows of a packed one (stage_pack_ctx_rows), read through the table by
+ *             stage_layernorm_gather_* / stage_l2norm_gather_fwd / stage_feat16_ln_*.  (NULL is the dense form, never an error.)
+ *   arena     carves the normalised image xn only for l2 != 0 with fp32 rows; pass the same M, l2 and dtype to the size query.
+ * The backward scratch does not depend on the form.  Refused before a launch with STAGE_ERR_SHAPE: a dtype outside the three;
+ * fp32 forward: M <= 0, K0 / H / D not a multiple of 4 or above 1024; half rows, forward and backward: M <= 0 or >= 2^31, H / D not
+ * a positive multiple of 4 or above 1024, a K0 that stage_feat16_supported declines, x NULL or not 8-byte aligned.  A buffer smaller
+ * than its query names: STAGE_ERR_WORKSPACE.                                                                                    */
+size_t stage_grp_input_mlp_arena_bytes(long long M, int K0, int H, int D, int l2, int dtype);
+int stage_grp_input_mlp_fwd(const void* x, int dtype, const int* src_rows, const float* const* params, float* out, void* arena,
+                            size_t arena_bytes, int* flags, long long M, int K0, int H, int D, int l2, float p_drop,
+                            const unsigned long long* seeds, void* stream);
 size_t stage_grp_input_mlp_bwd_tmp_bytes(long long M, int K0, int H, int D);
-int stage_grp_input_mlp_bwd(const float* dout, const float* x, const float* const* params, float* const* grads,
-                            const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M,
-                            int K0, int H, int D, int l2, float p_drop, const unsigned long long* seeds, void* stream);
+int stage_grp_input_mlp_bwd(const float* dout, const void* x, int dtype, const int* src_rows, const float* const* params,
+                            float* const* grads, const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes,
+                            long long M, int K0, int H, int D, int l2, float p_drop, const unsigned long long* seeds, void* stream);
 /* G2 encoder block without self-attention (model/encoder.py:29-52, model/cnn.py:37-47, model/position_encoding.py:38-43):
  * x (M, L, D), pe (>= L, D).  pool_mask (M, L) != NULL: out = masked max over L of the block's output (model/stage.py:503),
  * (M, D); otherwise out (M, L, D).  params / grads: per conv i (ln_g ln_b dw_w dw_b pw_w pw_b), then final_g final_b;
@@ -480,21 +485,18 @@ int stage_att_hard_negatives(const float* scores, const long long* row_off, cons
                              const int* slot_begin, const int* slot_q, int K, int M, int Lr, long long n_scores,
                              long long* flat_neg, void* stream);
 /* G6 proposal pooling + answer classifier (model/stage.py:420-467, 526-536): first (N*NA, Li, D), mask (N*NA, Li), glob / idx_g =
- * stage_masked_max_fwd(first, mask) computed ahead; meta (device int32) = src[P] | win[2P] | inv[2N] (proposal -> example, frame
- * window [st, ed), example -> its <= 2 proposals or -1; more per example: stage_grp_pool_cls_bwd_s).  logits (P*NA).  params / grads: ln_g ln_b W c (2D wide); seeds[1].
+ * stage_masked_max_fwd(first, mask) computed ahead; meta (device int32) = src[P] | win[2P] | inv[slots * N] (proposal -> example,
+ * frame window [st, ed), example -> its proposals or -1: below).  logits (P*NA).  params / grads: ln_g ln_b W c (2D wide); seeds[1].
  * d_first (N*NA, Li, D) receives both pooling paths.                                                                          */
 size_t stage_grp_pool_cls_arena_bytes(long long P, int NA, int D);
 int stage_grp_pool_cls_fwd(const float* first, const float* mask, const float* glob, const int* meta, const float* const* params,
                            float* logits, void* arena, size_t arena_bytes, int N, int NA, int Li, int D, long long P, float p_drop,
                            const unsigned long long* seeds, void* stream);
 size_t stage_grp_pool_cls_bwd_tmp_bytes(long long P, int NA, int D);
-int stage_grp_pool_cls_bwd(const float* d_logits, const float* mask, const int* idx_g, const int* meta, const float* const* params,
-                           float* const* grads, float* d_first, const void* arena, size_t arena_bytes, void* tmp, size_t tmp_bytes,
-                           int N, int NA, int Li, int D, long long P, float p_drop, const unsigned long long* seeds, void* stream);
-/* The same backward with up to `slots` proposals per example (max_num_proposal = slots - 1 predicted spans + the label's):
+/* The backward, with up to `slots` proposals per example (max_num_proposal = slots - 1 predicted spans + the label's):
  * meta = src[P] | win[2P] | inv[slots * N], inv (N, slots) = the example's proposals in ascending slot order or -1; the sums over
  * an example's proposals run in that order.  1 <= slots <= STAGE_TOPK_MAX + 1 (STAGE_ERR_SHAPE otherwise).  The forward reads src
- * and win only and needs no counterpart; stage_grp_pool_cls_bwd is this call with slots = 2.                                     */
+ * and win only and needs no counterpart.                                                                                         */
 int stage_grp_pool_cls_bwd_s(const float* d_logits, const float* mask, const int* idx_g, const int* meta, const float* const* params,
                              float* const* grads, float* d_first, const void* arena, size_t arena_bytes, void* tmp, size_t tmp_bytes,
                              int N, int NA, int Li, int D, long long P, int slots, float p_drop, const unsigned long long* seeds,
@@ -561,7 +563,7 @@ int stage_rag_ctx_rows(const int* cq, long long frames, int L, int* src_rows, vo
  * owning packed rows ptab[f].x .. ptab[f].x + ptab[f].y - 1 (ptab (frames, 2) int32: first packed row, len <= L) -- followed by ONE zero
  * row, the source of every padded position (the collate zero-fills behind a frame's length: tvqa_dataset.py:515-553).
  * stage_pack_ctx_rows: stage_rag_ctx_rows for such a stream -- src_rows[cq[f].x + l] = l < ptab[f].y ? ptab[f].x + l : zero_row for
- * l < cq[f].y; the *_rag input-MLP groups then read the packed buffer through the table.  L < 1 or frames * L >= 2^31:
+ * l < cq[f].y; the input-MLP group then reads the packed buffer through the table.  L < 1 or frames * L >= 2^31:
  * STAGE_ERR_SHAPE, nothing launched.
  * stage_pack_unpack: the padded image for the paths that keep dense tensors.  EVERY row of dense (frames, L, row_bytes) is written in
  * one pass: row l < len is a byte copy of packed row start + l, every other row is zeros (no memset needed, any element type);
@@ -576,12 +578,6 @@ int stage_layernorm_gather_bwd(const float* dy, const float* x, const int* gathe
                                const float* gamma, float* dgamma, float* dbeta, long long rows, int K, float p_drop,
                                unsigned long long seed, void* ws, size_t ws_bytes, void* stream);
 int stage_l2norm_gather_fwd(const float* x, const int* gather, float* y, long long rows, int K, float eps, void* stream);
-int stage_grp_input_mlp_rag_fwd(const float* x, const int* src_rows, const float* const* P, float* out, void* arena,
-                                size_t arena_bytes, int* flags, long long M, int K0, int H, int D, int l2, float p,
-                                const unsigned long long* seeds, void* stream);
-int stage_grp_input_mlp_rag_bwd(const float* dout, const float* x, const int* src_rows, const float* const* P, float* const* G,
-                                const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M,
-                                int K0, int H, int D, int l2, float p, const unsigned long long* seeds, void* stream);
 /* HALF-PRECISION FEATURE ROWS in the fp32 model (csrc/feat16.hip).  A loader may store the BERT / region features as fp16 or bf16
  * (half the host -> device bytes); these entry points read such rows in place and convert them in registers -- exactly -- so that no
  * fp32 image of the features (and, with l2, no normalised image) is ever written.  dtype: STAGE_DT_F16 / STAGE_DT_BF16.
@@ -591,6 +587,7 @@ int stage_grp_input_mlp_rag_bwd(const float* dout, const float* x, const int* sr
  * upcast rows.  The backward gives d gamma / d beta only (features are data), through a deterministic two-stage column reduction.
  * Requirements: K0 % 4 == 0, 4 <= K0 <= 1024 (stage_feat16_supported), x 8-byte aligned with contiguous rows, rows < 2^31; anything
  * else returns STAGE_ERR_SHAPE before a launch. */
+#define STAGE_DT_F32 0    /* (stage_grp_input_mlp_* only: the entry points below take half-precision rows) */
 #define STAGE_DT_F16 1
 #define STAGE_DT_BF16 2
 int stage_feat16_supported(int K0, int dtype);
@@ -601,23 +598,6 @@ size_t stage_feat16_ln_bwd_ws_bytes(int K0);
 int stage_feat16_ln_bwd(const float* dy0, const void* x, int dtype, const int* src_rows, const float* mean0, const float* rstd0,
                         float* dgamma, float* dbeta, long long rows, int K0, int l2, float eps_l2, float p_drop,
                         unsigned long long seed, void* ws, size_t ws_bytes, void* stream);
-/* G1 / its ragged form on half-precision features (model/stage.py:350-362 as stage_grp_input_mlp_*): the first stage above, then the
- * unchanged Linear / LayerNorm chain.  Same params / grads / seeds / flags; the arena holds no normalised image (its size does not depend
- * on l2); the backward scratch is stage_grp_input_mlp_bwd_tmp_bytes.  src_rows as in stage_grp_input_mlp_rag_*. */
-size_t stage_grp_input_mlp_h_arena_bytes(long long M, int K0, int H, int D);
-int stage_grp_input_mlp_h_fwd(const void* x, int dtype, const float* const* params, float* out, void* arena, size_t arena_bytes,
-                              int* flags, long long M, int K0, int H, int D, int l2, float p_drop, const unsigned long long* seeds,
-                              void* stream);
-int stage_grp_input_mlp_h_bwd(const float* dout, const void* x, int dtype, const float* const* params, float* const* grads,
-                              const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M,
-                              int K0, int H, int D, int l2, float p_drop, const unsigned long long* seeds, void* stream);
-int stage_grp_input_mlp_rag_h_fwd(const void* x, int dtype, const int* src_rows, const float* const* params, float* out, void* arena,
-                                  size_t arena_bytes, int* flags, long long M, int K0, int H, int D, int l2, float p_drop,
-                                  const unsigned long long* seeds, void* stream);
-int stage_grp_input_mlp_rag_h_bwd(const float* dout, const void* x, int dtype, const int* src_rows, const float* const* params,
-                                  float* const* grads, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
-                                  size_t tmp_bytes, long long M, int K0, int H, int D, int l2, float p_drop,
-                                  const unsigned long long* seeds, void* stream);
 int stage_rag_fill_pooled(float* out, int* argmax, long long rows, int D, void* stream);      /* -1e10 / 0: model/stage.py:503 on an all-masked group */
 int stage_rag_zero_dump(float* A_fc, const int* fmap, int N, int NA, int Li, int Lqa, int D, void* stream);
 /* K1 with a frame-compact A / dA (model/context_query_attention.py:35-101; D == 128, the fast kernels only) */

@@ -7,11 +7,10 @@ import pytest
 
 from conftest import ROOT
 
-F16, BF16 = 1, 2        # include/stage_hip.h: STAGE_DT_F16 / STAGE_DT_BF16
+F32, F16, BF16 = 0, 1, 2        # include/stage_hip.h: STAGE_DT_F32 / STAGE_DT_F16 / STAGE_DT_BF16
 
 SYMBOLS = ["stage_feat16_supported", "stage_feat16_ln_fwd", "stage_feat16_ln_bwd_ws_bytes", "stage_feat16_ln_bwd",
-           "stage_grp_input_mlp_h_arena_bytes", "stage_grp_input_mlp_h_fwd", "stage_grp_input_mlp_h_bwd",
-           "stage_grp_input_mlp_rag_h_fwd", "stage_grp_input_mlp_rag_h_bwd"]
+           "stage_grp_input_mlp_arena_bytes", "stage_grp_input_mlp_fwd", "stage_grp_input_mlp_bwd"]
 
 
 @pytest.fixture(scope="module")
@@ -27,10 +26,10 @@ def test_symbols_exported_and_bound(lib):
     for name in SYMBOLS:
         assert hasattr(lib, name), name
         assert name in _lib.SIGNATURES, name
-    assert (_lib.STAGE_DT_F16, _lib.STAGE_DT_BF16) == (F16, BF16)
+    assert (_lib.STAGE_DT_F32, _lib.STAGE_DT_F16, _lib.STAGE_DT_BF16) == (F32, F16, BF16)
     hdr = open(os.path.join(ROOT, "include", "stage_hip.h")).read()
-    assert "#define STAGE_DT_F16 1" in hdr and "#define STAGE_DT_BF16 2" in hdr
-    assert lib.stage_hip_abi_version() == 5          # added symbols keep the version
+    assert "#define STAGE_DT_F32 0" in hdr and "#define STAGE_DT_F16 1" in hdr and "#define STAGE_DT_BF16 2" in hdr
+    assert lib.stage_hip_abi_version() == 6
 
 
 def test_supported_truth_table(lib):
@@ -49,7 +48,9 @@ def test_size_queries_need_no_gpu(lib):
         assert ws >= 2 * K0 * 4                       # at least one [2][K0] partial row
         assert ws == lib.stage_ln_bwd_ws_bytes(K0)    # the input-MLP group's backward scratch (sized for the fp32 kernel) serves both
     for M, K0, H, D in ((1, 4, 8, 8), (67, 300, 300, 128), (1031, 768, 300, 128), (96000, 300, 300, 128), (240000, 768, 300, 128)):
-        new = lib.stage_grp_input_mlp_h_arena_bytes(M, K0, H, D)
-        old_l2 = lib.stage_grp_input_mlp_arena_bytes(M, K0, H, D, 1)
-        assert 0 < new <= old_l2 - M * K0 * 4, (M, K0, new, old_l2)       # no normalised image
-        assert new == lib.stage_grp_input_mlp_arena_bytes(M, K0, H, D, 0)
+        old_l2 = lib.stage_grp_input_mlp_arena_bytes(M, K0, H, D, 1, F32)
+        for dt in (F16, BF16):
+            for l2 in (0, 1):
+                new = lib.stage_grp_input_mlp_arena_bytes(M, K0, H, D, l2, dt)
+                assert 0 < new <= old_l2 - M * K0 * 4, (M, K0, new, old_l2)       # no normalised image
+                assert new == lib.stage_grp_input_mlp_arena_bytes(M, K0, H, D, 0, F32)

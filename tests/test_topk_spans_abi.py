@@ -33,10 +33,9 @@ def test_new_symbols_in_header_binding_and_library():
     assert _lib.SIGNATURES["stage_topk_spans_supported"] == (I, [I, I])
     assert _lib.SIGNATURES["stage_gt_spans_topk"] == (I, [P, P, P, P, P, I, I, I, I, P])
     assert _lib.SIGNATURES["stage_topk_spans"] == (I, [P, I, P, P, LL, I, I, P])
-    old, new = _lib.SIGNATURES["stage_grp_pool_cls_bwd"][1], _lib.SIGNATURES["stage_grp_pool_cls_bwd_s"][1]
-    assert new == old[:16] + [I] + old[16:]                      # the old list with `slots` behind P
-    # symbols were added, none changed: the ABI version stays
-    assert int(re.search(r"#define STAGE_HIP_ABI_VERSION (\d+)", hdr).group(1)) == 5 == _lib.ABI_VERSION == lib.stage_hip_abi_version()
+    SZ = _lib.SZ
+    assert _lib.SIGNATURES["stage_grp_pool_cls_bwd_s"] == (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, I, F, P, P])    # `slots` behind P
+    assert int(re.search(r"#define STAGE_HIP_ABI_VERSION (\d+)", hdr).group(1)) == 6 == _lib.ABI_VERSION == lib.stage_hip_abi_version()
     assert int(re.search(r"#define STAGE_TOPK_MAX (\d+)", hdr).group(1)) == 8 == _lib.STAGE_TOPK_MAX
 
 

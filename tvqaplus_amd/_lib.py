@@ -30,8 +30,6 @@ SIGNATURES = {
     "stage_str_attn_bwd_fused_ws_bytes": (SZ, [I, I, I, I, I]),
     "stage_str_attn_bwd_fused": (I, [P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, P, SZ, P]),
     "stage_str_attn_long_fwd": (I, [P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P]),
-    "stage_str_attn_long_bwd_ws_bytes": (SZ, [I, I, I, I]),
-    "stage_str_attn_long_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P, SZ, P]),
     "stage_str_attn_long_bwd_qm_ws_bytes": (SZ, [I, I, I, I, I]),
     "stage_str_attn_long_bwd_qm": (I, [P, P, P, P, P, P, P, P, P, P, P, P, I, I, I, I, I, I, F, I, P, SZ, P]),
     "stage_l2norm_fwd": (I, [P, P, P, LL, I, F, F, U64, P]),
@@ -53,7 +51,6 @@ SIGNATURES = {
     "stage_gemm_mask_supported": (I, [LL, I, I]),
     "stage_gemm_nt_mask": (I, [P, P, P, P, P, P, LL, I, I, I, P]),
     "stage_gemm_tn_mask": (I, [P, P, P, P, P, LL, I, I, P, SZ, P]),
-    "stage_add_pe": (I, [P, P, P, LL, I, I, P]),
     "stage_dwconv_fwd": (I, [P, P, P, P, LL, I, I, I, P]),
     "stage_dwconv_bwd_ws_bytes": (SZ, [I, I]),
     "stage_dwconv_bwd": (I, [P, P, P, P, P, P, LL, I, I, I, P, SZ, P]),
@@ -106,10 +103,10 @@ SIGNATURES = {
     "stage_cat3_ln_gemm_fwd": (I, [P, P, P, P, P, P, P, P, P, P, P, LL, I, I, I, F, F, U64, P, SZ, P]),
     # K-groups (csrc/groups.hip): one forward and one backward symbol per fused-op group; params / grads / seeds / flags are
     # HOST arrays (pointers to them travel as void*)
-    "stage_grp_input_mlp_arena_bytes": (SZ, [LL, I, I, I, I]),
-    "stage_grp_input_mlp_fwd": (I, [P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
+    "stage_grp_input_mlp_arena_bytes": (SZ, [LL, I, I, I, I, I]),
+    "stage_grp_input_mlp_fwd": (I, [P, I, P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
     "stage_grp_input_mlp_bwd_tmp_bytes": (SZ, [LL, I, I, I]),
-    "stage_grp_input_mlp_bwd": (I, [P, P, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
+    "stage_grp_input_mlp_bwd": (I, [P, P, I, P, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
     "stage_grp_encoder_arena_bytes": (SZ, [LL, I, I, I, I]),
     "stage_grp_encoder_fwd": (I, [P, P, P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
     "stage_grp_encoder_bwd_tmp_bytes": (SZ, [LL, I, I, I, I]),
@@ -145,7 +142,6 @@ SIGNATURES = {
     "stage_grp_pool_cls_arena_bytes": (SZ, [LL, I, I]),
     "stage_grp_pool_cls_fwd": (I, [P, P, P, P, P, P, P, SZ, I, I, I, I, LL, F, P, P]),
     "stage_grp_pool_cls_bwd_tmp_bytes": (SZ, [LL, I, I]),
-    "stage_grp_pool_cls_bwd": (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, F, P, P]),
     "stage_grp_pool_cls_bwd_s": (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, I, F, P, P]),
     # the proposal decision on the device (csrc/proposals.hip): thd_host is a HOST array of two doubles {iou_thd, ce_prob_thd}
     "stage_proposal_meta": (I, [P, I, I, P, I, P, P, P, P]),
@@ -167,18 +163,11 @@ SIGNATURES = {
     "stage_layernorm_gather_fwd": (I, [P, P, P, P, P, P, P, LL, I, F, F, U64, P]),
     "stage_layernorm_gather_bwd": (I, [P, P, P, P, P, P, P, P, LL, I, F, U64, P, SZ, P]),
     "stage_l2norm_gather_fwd": (I, [P, P, P, LL, I, F, P]),
-    "stage_grp_input_mlp_rag_fwd": (I, [P, P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
-    "stage_grp_input_mlp_rag_bwd": (I, [P, P, P, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
-    # half-precision feature rows in the fp32 model (csrc/feat16.hip): first stage of the input MLP, and G1 / its ragged form on it
+    # half-precision feature rows in the fp32 model (csrc/feat16.hip): first stage of the input MLP
     "stage_feat16_supported": (I, [I, I]),
     "stage_feat16_ln_fwd": (I, [P, I, P, P, P, P, P, P, LL, I, I, F, F, F, U64, P]),
     "stage_feat16_ln_bwd_ws_bytes": (SZ, [I]),
     "stage_feat16_ln_bwd": (I, [P, P, I, P, P, P, P, P, LL, I, I, F, F, U64, P, SZ, P]),
-    "stage_grp_input_mlp_h_arena_bytes": (SZ, [LL, I, I, I]),
-    "stage_grp_input_mlp_h_fwd": (I, [P, I, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
-    "stage_grp_input_mlp_h_bwd": (I, [P, P, I, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
-    "stage_grp_input_mlp_rag_h_fwd": (I, [P, I, P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
-    "stage_grp_input_mlp_rag_h_bwd": (I, [P, P, I, P, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
     "stage_cat3_ln_gemm_fwd_rag_supported": (I, [LL, LL, LL, I]),
     "stage_cat3_ln_gemm_fwd_rag": (I, [P, P, P, P, P, P, P, P, P, P, P, P, LL, LL, LL, I, F, F, U64, P, SZ, P]),
     "stage_cat3_dx_ln_bwd_rag_supported": (I, [LL, LL, I, I, I, I]),
@@ -218,7 +207,7 @@ SIGNATURES = {
     "stage_grounding_update": (I, [P, LL, P, LL, P, LL, P, I, P, LL, P, LL, I, I, F, F, P]),
 }
 
-ABI_VERSION = 5    # include/stage_hip.h: STAGE_HIP_ABI_VERSION (tests/test_abi.py holds the two together)
+ABI_VERSION = 6    # include/stage_hip.h: STAGE_HIP_ABI_VERSION (tests/test_abi.py holds the two together)
 
 _lib = None
 
@@ -255,7 +244,7 @@ def load() -> ctypes.CDLL:
     return lib
 
 
-STAGE_DT_F16, STAGE_DT_BF16 = 1, 2     # include/stage_hip.h: dtype codes of the half-precision feature entry points
+STAGE_DT_F32, STAGE_DT_F16, STAGE_DT_BF16 = 0, 1, 2     # include/stage_hip.h: dtype codes of the feature rows
 
 STAGE_TOPK_MAX = 8        # include/stage_hip.h: the largest K of the top-K span kernels (max_num_proposal, n_best)
 

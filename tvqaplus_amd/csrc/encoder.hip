@@ -10,26 +10,6 @@
 #define GRID_CAP 4096
 #define DW_PART_CAP 512
 
-__global__ __launch_bounds__(256) void add_pe_kernel(const float* __restrict__ x, const float* __restrict__ pe,
-                                                     float* __restrict__ y, long rows, int L, int D4) {
-    const long total = rows * D4;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const long row = e / D4;
-        const int q = (int)(e % D4);
-        const int l = (int)(row % L);
-        st4(y + e * 4, f4add(ld4(x + e * 4), ld4(pe + ((long)l * D4 + q) * 4)));
-    }
-}
-
-extern "C" int stage_add_pe(const float* x, const float* pe, float* y, long long M, int L, int D, void* stream) {
-    if (M <= 0) return 0;
-    if (D % 4 != 0) return STAGE_ERR_SHAPE;
-    const int grid = stage_grid_for(M * L * (D / 4), 256, GRID_CAP);
-    hipLaunchKernelGGL(add_pe_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, x, pe, y, (long)(M * L), L, D / 4);
-    STAGE_LAUNCH_CHECK();
-    return 0;
-}
-
 // out[m,l,:] = bias + sum_t w[:,t] * in[m, l+t-pad, :]           w: (D,1,k) as stored by nn.Conv1d
 template <typename T>
 __global__ __launch_bounds__(256) void dwconv_fwd_kernel(const T* __restrict__ in, const float* __restrict__ w,

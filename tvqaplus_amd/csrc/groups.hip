@@ -109,16 +109,18 @@ bool cat3_reduced_ok(int D, int rep, int inner) {
 // G1  input MLP (model/stage.py:350-362 base_encoder up to the encoder; :85-91 / :98-104 bridge, :115-120 input_embedding;
 //     l2 != 0: the F.normalize of :256 first):  [l2norm] -> LN(K0)+drop -> Linear(K0->H)+ReLU -> LN(H)+drop -> Linear(H->D)+ReLU -> LN(D)
 //     params: g0 b0 W1 c1 g1 b1 W2 c2 g2 b2 ; seeds: [LN0 dropout, LN1 dropout] ; flags: [mask1, mask2]
+//     One body per direction; only the first stage has forms: fp32 rows or fp16 / bf16 rows read in place (csrc/feat16.hip), every
+//     row or the rows a src_rows table names (ragged / packed context rows: csrc/ragged.hip), with or without the l2norm.
 // =====================================================================================================================
 struct MlpArena {
     float *xn, *y0, *mean0, *rstd0, *h1, *y1, *mean1, *rstd1, *h2, *mean2, *rstd2;
     unsigned *mask1, *mask2;
     size_t bytes;
 };
-MlpArena mlp_layout(void* base, long long M, int K0, int H, int D, int l2) {
+MlpArena mlp_layout(void* base, long long M, int K0, int H, int D, int l2, int dtype) {
     Bump b{(char*)base, 0};
     MlpArena a;
-    a.xn = l2 ? b.take<float>((size_t)M * K0) : nullptr;
+    a.xn = l2 && dtype == STAGE_DT_F32 ? b.take<float>((size_t)M * K0) : nullptr;   // half rows are normalised in registers
     a.y0 = b.take<float>((size_t)M * K0);
     a.mean0 = b.take<float>((size_t)M);
     a.rstd0 = b.take<float>((size_t)M);
@@ -135,53 +137,42 @@ MlpArena mlp_layout(void* base, long long M, int K0, int H, int D, int l2) {
     return a;
 }
 
-}  // namespace
-
-extern "C" size_t stage_grp_input_mlp_arena_bytes(long long M, int K0, int H, int D, int l2) {
-    return mlp_layout(nullptr, M, K0, H, D, l2).bytes;
-}
-
-namespace {
-// gather != NULL (ragged context rows): the M rows are rows gather[0..M) of the padded feature tensor x
-int input_mlp_fwd(const float* x, const int* gather, const float* const* P, float* out, void* arena, size_t arena_bytes, int* flags,
-                  long long M, int K0, int H, int D, int l2, float p, const unsigned long long* seeds, void* st);
-}
-extern "C" int stage_grp_input_mlp_fwd(const float* x, const float* const* P, float* out, void* arena, size_t arena_bytes,
-                                       int* flags, long long M, int K0, int H, int D, int l2, float p,
-                                       const unsigned long long* seeds, void* st) {
-    return input_mlp_fwd(x, nullptr, P, out, arena, arena_bytes, flags, M, K0, H, D, l2, p, seeds, st);
-}
-// ragged context rows (csrc/ragged.hip): x is the padded (frames * L, K0) feature tensor, src_rows (M) its live rows in order
-extern "C" int stage_grp_input_mlp_rag_fwd(const float* x, const int* src_rows, const float* const* P, float* out, void* arena,
-                                           size_t arena_bytes, int* flags, long long M, int K0, int H, int D, int l2, float p,
-                                           const unsigned long long* seeds, void* st) {
-    if (!src_rows) return STAGE_ERR_SHAPE;
-    return input_mlp_fwd(x, src_rows, P, out, arena, arena_bytes, flags, M, K0, H, D, l2, p, seeds, st);
-}
-namespace {
-int input_mlp_fwd(const float* x, const int* gather, const float* const* P, float* out, void* arena, size_t arena_bytes, int* flags,
-                  long long M, int K0, int H, int D, int l2, float p, const unsigned long long* seeds, void* st) {
-    if (M <= 0 || K0 % 4 || H % 4 || D % 4 || K0 > 1024 || H > 1024 || D > 1024) return STAGE_ERR_SHAPE;
-    MlpArena a = mlp_layout(arena, M, K0, H, D, l2);
-    if (arena_bytes < a.bytes) return STAGE_ERR_WORKSPACE;
-    const float* xin = x;
+// first stage: [l2norm] -> LN(K0)+dropout over rows src_rows[0..M) of x (NULL: rows 0..M) -> y0, mean0, rstd0
+int mlp_first_fwd(const void* x, int dtype, const int* src_rows, const float* const* P, const MlpArena& a, long long M, int K0, int l2,
+                  float p, unsigned long long seed, void* st) {
+    if (dtype != STAGE_DT_F32)
+        return stage_feat16_ln_fwd(x, dtype, src_rows, P[0], P[1], a.y0, a.mean0, a.rstd0, M, K0, l2, EPS_LN, EPS_L2, p, seed, st);
+    const float* xf = (const float*)x;
+    if (src_rows && !l2) return stage_layernorm_gather_fwd(xf, src_rows, P[0], P[1], a.y0, a.mean0, a.rstd0, M, K0, EPS_LN, p, seed, st);
     if (l2) {
-        if (gather) TRY(stage_l2norm_gather_fwd(x, gather, a.xn, M, K0, EPS_L2, st));
-        else TRY(stage_l2norm_fwd(x, a.xn, nullptr, M, K0, EPS_L2, 0.f, 0ull, st));
-        xin = a.xn;
+        if (src_rows) TRY(stage_l2norm_gather_fwd(xf, src_rows, a.xn, M, K0, EPS_L2, st));
+        else TRY(stage_l2norm_fwd(xf, a.xn, nullptr, M, K0, EPS_L2, 0.f, 0ull, st));
+        xf = a.xn;
     }
-    if (gather && !l2) TRY(stage_layernorm_gather_fwd(x, gather, P[0], P[1], a.y0, a.mean0, a.rstd0, M, K0, EPS_LN, p, seeds[0], st));
-    else
-    TRY(stage_layernorm_fwd(xin, nullptr, 0, nullptr, P[0], P[1], a.y0, a.mean0, a.rstd0, M, K0, EPS_LN, p, seeds[0], st));
-    TRY(lin_fwd(a.y0, P[2], P[3], a.h1, a.mask1, &flags[0], M, H, K0, 1, st));
-    TRY(stage_layernorm_fwd(a.h1, nullptr, 0, nullptr, P[4], P[5], a.y1, a.mean1, a.rstd1, M, H, EPS_LN, p, seeds[1], st));
-    TRY(lin_fwd(a.y1, P[6], P[7], a.h2, a.mask2, &flags[1], M, D, H, 1, st));
-    TRY(stage_layernorm_fwd(a.h2, nullptr, 0, nullptr, P[8], P[9], out, a.mean2, a.rstd2, M, D, EPS_LN, 0.f, 0ull, st));
-    return 0;
+    return stage_layernorm_fwd(xf, nullptr, 0, nullptr, P[0], P[1], a.y0, a.mean0, a.rstd0, M, K0, EPS_LN, p, seed, st);
 }
-}  // namespace
+// its backward: d gamma / d beta only (the features are data)
+int mlp_first_bwd(const float* dy0, const void* x, int dtype, const int* src_rows, const float* const* P, float* const* G, const MlpArena& a,
+                  long long M, int K0, int l2, float p, unsigned long long seed, void* ws, void* st) {
+    if (dtype != STAGE_DT_F32)
+        return stage_feat16_ln_bwd(dy0, x, dtype, src_rows, a.mean0, a.rstd0, G[0], G[1], M, K0, l2, EPS_L2, p, seed, ws,
+                                   stage_feat16_ln_bwd_ws_bytes(K0), st);
+    if (src_rows && !l2)
+        return stage_layernorm_gather_bwd(dy0, (const float*)x, src_rows, a.mean0, a.rstd0, P[0], G[0], G[1], M, K0, p, seed, ws,
+                                          stage_ln_bwd_ws_bytes(K0), st);
+    return stage_layernorm_bwd(dy0, l2 ? a.xn : (const float*)x, a.mean0, a.rstd0, P[0], nullptr, nullptr, G[0], G[1], M, K0, p, seed, ws,
+                               stage_ln_bwd_ws_bytes(K0), st);
+}
+// what each form refuses before a launch (the fp32 backward checks its buffers only); a dtype that is none of the three is declined
+// as half rows: stage_feat16_supported knows STAGE_DT_F16 and STAGE_DT_BF16 alone
+bool mlp_f32_ok(long long M, int K0, int H, int D) {
+    return M > 0 && K0 % 4 == 0 && H % 4 == 0 && D % 4 == 0 && K0 <= 1024 && H <= 1024 && D <= 1024;
+}
+bool mlp_half_ok(const void* x, int dtype, long long M, int K0, int H, int D) {
+    return M > 0 && M < (1ll << 31) && H % 4 == 0 && D % 4 == 0 && H > 0 && D > 0 && H <= 1024 && D <= 1024 &&
+           stage_feat16_supported(K0, dtype) && x && ((uintptr_t)x & 7) == 0;
+}
 
-namespace {
 struct MlpTmp { float *dh2, *dy1, *dh1, *dy0, *wt; void* ws; size_t wsb, bytes; };
 MlpTmp mlp_tmp(void* base, long long M, int K0, int H, int D) {
     Bump b{(char*)base, 0};
@@ -197,105 +188,43 @@ MlpTmp mlp_tmp(void* base, long long M, int K0, int H, int D) {
     t.bytes = b.off;
     return t;
 }
+
 }  // namespace
 
+extern "C" size_t stage_grp_input_mlp_arena_bytes(long long M, int K0, int H, int D, int l2, int dtype) {
+    return mlp_layout(nullptr, M, K0, H, D, l2, dtype).bytes;
+}
 extern "C" size_t stage_grp_input_mlp_bwd_tmp_bytes(long long M, int K0, int H, int D) { return mlp_tmp(nullptr, M, K0, H, D).bytes; }
 
-// grads: same order as params (dg0 db0 dW1 dc1 dg1 db1 dW2 dc2 dg2 db2).  The features need no gradient (they are data).
-namespace {
-int input_mlp_bwd(const float* dout, const float* x, const int* gather, const float* const* P, float* const* G, const void* arena,
-                  size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M, int K0, int H, int D, int l2, float p,
-                  const unsigned long long* seeds, void* st);
-}
-extern "C" int stage_grp_input_mlp_bwd(const float* dout, const float* x, const float* const* P, float* const* G, const void* arena,
-                                       size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M, int K0,
-                                       int H, int D, int l2, float p, const unsigned long long* seeds, void* st) {
-    return input_mlp_bwd(dout, x, nullptr, P, G, arena, arena_bytes, flags, tmp, tmp_bytes, M, K0, H, D, l2, p, seeds, st);
-}
-extern "C" int stage_grp_input_mlp_rag_bwd(const float* dout, const float* x, const int* src_rows, const float* const* P,
-                                           float* const* G, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
-                                           size_t tmp_bytes, long long M, int K0, int H, int D, int l2, float p,
-                                           const unsigned long long* seeds, void* st) {
-    if (!src_rows) return STAGE_ERR_SHAPE;
-    return input_mlp_bwd(dout, x, src_rows, P, G, arena, arena_bytes, flags, tmp, tmp_bytes, M, K0, H, D, l2, p, seeds, st);
-}
-namespace {
-int input_mlp_bwd(const float* dout, const float* x, const int* gather, const float* const* P, float* const* G, const void* arena,
-                  size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M, int K0, int H, int D, int l2, float p,
-                  const unsigned long long* seeds, void* st) {
-    MlpArena a = mlp_layout((void*)arena, M, K0, H, D, l2);
-    MlpTmp t = mlp_tmp(tmp, M, K0, H, D);
-    if (arena_bytes < a.bytes || tmp_bytes < t.bytes) return STAGE_ERR_WORKSPACE;
-    const float* xin = l2 ? a.xn : x;
-    TRY(stage_layernorm_bwd(dout, a.h2, a.mean2, a.rstd2, P[8], t.dh2, nullptr, G[8], G[9], M, D, 0.f, 0ull, t.ws, stage_ln_bwd_ws_bytes(D), st));
-    TRY(lin_bwd(t.dh2, a.y1, a.h2, a.mask2, flags[1], 1, P[6], t.wt, t.dy1, G[6], G[7], M, D, H, t.ws, t.wsb, st));
-    TRY(stage_layernorm_bwd(t.dy1, a.h1, a.mean1, a.rstd1, P[4], t.dh1, nullptr, G[4], G[5], M, H, p, seeds[1], t.ws, stage_ln_bwd_ws_bytes(H), st));
-    TRY(lin_bwd(t.dh1, a.y0, a.h1, a.mask1, flags[0], 1, P[2], t.wt, t.dy0, G[2], G[3], M, H, K0, t.ws, t.wsb, st));
-    if (gather && !l2)
-        return stage_layernorm_gather_bwd(t.dy0, x, gather, a.mean0, a.rstd0, P[0], G[0], G[1], M, K0, p, seeds[0], t.ws, stage_ln_bwd_ws_bytes(K0), st);
-    TRY(stage_layernorm_bwd(t.dy0, xin, a.mean0, a.rstd0, P[0], nullptr, nullptr, G[0], G[1], M, K0, p, seeds[0], t.ws, stage_ln_bwd_ws_bytes(K0), st));
-    return 0;
-}
-}  // namespace
-
-// G1 on HALF-PRECISION features (csrc/feat16.hip): x holds fp16 / bf16 rows that the first stage reads in place -- no fp32 image, and
-// with l2 no normalised image either (the arena is the l2 == 0 layout: xn is never carved); behind the first stage, the chain above.
-extern "C" size_t stage_grp_input_mlp_h_arena_bytes(long long M, int K0, int H, int D) { return mlp_layout(nullptr, M, K0, H, D, 0).bytes; }
-
-namespace {
-bool input_mlp_h_ok(const void* x, int dtype, long long M, int K0, int H, int D) {
-    return M > 0 && M < (1ll << 31) && H % 4 == 0 && D % 4 == 0 && H > 0 && D > 0 && H <= 1024 && D <= 1024 &&
-           stage_feat16_supported(K0, dtype) && x && ((uintptr_t)x & 7) == 0;
-}
-int input_mlp_h_fwd(const void* x, int dtype, const int* gather, const float* const* P, float* out, void* arena, size_t arena_bytes,
-                    int* flags, long long M, int K0, int H, int D, int l2, float p, const unsigned long long* seeds, void* st) {
-    if (!input_mlp_h_ok(x, dtype, M, K0, H, D)) return STAGE_ERR_SHAPE;
-    MlpArena a = mlp_layout(arena, M, K0, H, D, 0);
+extern "C" int stage_grp_input_mlp_fwd(const void* x, int dtype, const int* src_rows, const float* const* P, float* out, void* arena,
+                                       size_t arena_bytes, int* flags, long long M, int K0, int H, int D, int l2, float p,
+                                       const unsigned long long* seeds, void* st) {
+    if (dtype == STAGE_DT_F32 ? !mlp_f32_ok(M, K0, H, D) : !mlp_half_ok(x, dtype, M, K0, H, D)) return STAGE_ERR_SHAPE;
+    MlpArena a = mlp_layout(arena, M, K0, H, D, l2, dtype);
     if (arena_bytes < a.bytes) return STAGE_ERR_WORKSPACE;
-    TRY(stage_feat16_ln_fwd(x, dtype, gather, P[0], P[1], a.y0, a.mean0, a.rstd0, M, K0, l2, EPS_LN, EPS_L2, p, seeds[0], st));
+    TRY(mlp_first_fwd(x, dtype, src_rows, P, a, M, K0, l2, p, seeds[0], st));
     TRY(lin_fwd(a.y0, P[2], P[3], a.h1, a.mask1, &flags[0], M, H, K0, 1, st));
     TRY(stage_layernorm_fwd(a.h1, nullptr, 0, nullptr, P[4], P[5], a.y1, a.mean1, a.rstd1, M, H, EPS_LN, p, seeds[1], st));
     TRY(lin_fwd(a.y1, P[6], P[7], a.h2, a.mask2, &flags[1], M, D, H, 1, st));
     TRY(stage_layernorm_fwd(a.h2, nullptr, 0, nullptr, P[8], P[9], out, a.mean2, a.rstd2, M, D, EPS_LN, 0.f, 0ull, st));
     return 0;
 }
-int input_mlp_h_bwd(const float* dout, const void* x, int dtype, const int* gather, const float* const* P, float* const* G,
-                    const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes, long long M, int K0, int H, int D,
-                    int l2, float p, const unsigned long long* seeds, void* st) {
-    if (!input_mlp_h_ok(x, dtype, M, K0, H, D)) return STAGE_ERR_SHAPE;
-    MlpArena a = mlp_layout((void*)arena, M, K0, H, D, 0);
+
+// grads: same order as params (dg0 db0 dW1 dc1 dg1 db1 dW2 dc2 dg2 db2).  The features need no gradient (they are data).
+extern "C" int stage_grp_input_mlp_bwd(const float* dout, const void* x, int dtype, const int* src_rows, const float* const* P,
+                                       float* const* G, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
+                                       size_t tmp_bytes, long long M, int K0, int H, int D, int l2, float p,
+                                       const unsigned long long* seeds, void* st) {
+    if (dtype != STAGE_DT_F32 && !mlp_half_ok(x, dtype, M, K0, H, D)) return STAGE_ERR_SHAPE;
+    MlpArena a = mlp_layout((void*)arena, M, K0, H, D, l2, dtype);
     MlpTmp t = mlp_tmp(tmp, M, K0, H, D);
-    if (arena_bytes < a.bytes || tmp_bytes < t.bytes || t.wsb < stage_feat16_ln_bwd_ws_bytes(K0)) return STAGE_ERR_WORKSPACE;
+    if (arena_bytes < a.bytes || tmp_bytes < t.bytes) return STAGE_ERR_WORKSPACE;
+    if (dtype != STAGE_DT_F32 && t.wsb < stage_feat16_ln_bwd_ws_bytes(K0)) return STAGE_ERR_WORKSPACE;
     TRY(stage_layernorm_bwd(dout, a.h2, a.mean2, a.rstd2, P[8], t.dh2, nullptr, G[8], G[9], M, D, 0.f, 0ull, t.ws, stage_ln_bwd_ws_bytes(D), st));
     TRY(lin_bwd(t.dh2, a.y1, a.h2, a.mask2, flags[1], 1, P[6], t.wt, t.dy1, G[6], G[7], M, D, H, t.ws, t.wsb, st));
     TRY(stage_layernorm_bwd(t.dy1, a.h1, a.mean1, a.rstd1, P[4], t.dh1, nullptr, G[4], G[5], M, H, p, seeds[1], t.ws, stage_ln_bwd_ws_bytes(H), st));
     TRY(lin_bwd(t.dh1, a.y0, a.h1, a.mask1, flags[0], 1, P[2], t.wt, t.dy0, G[2], G[3], M, H, K0, t.ws, t.wsb, st));
-    return stage_feat16_ln_bwd(t.dy0, x, dtype, gather, a.mean0, a.rstd0, G[0], G[1], M, K0, l2, EPS_L2, p, seeds[0], t.ws,
-                               stage_feat16_ln_bwd_ws_bytes(K0), st);
-}
-}  // namespace
-extern "C" int stage_grp_input_mlp_h_fwd(const void* x, int dtype, const float* const* P, float* out, void* arena, size_t arena_bytes,
-                                         int* flags, long long M, int K0, int H, int D, int l2, float p,
-                                         const unsigned long long* seeds, void* st) {
-    return input_mlp_h_fwd(x, dtype, nullptr, P, out, arena, arena_bytes, flags, M, K0, H, D, l2, p, seeds, st);
-}
-extern "C" int stage_grp_input_mlp_h_bwd(const float* dout, const void* x, int dtype, const float* const* P, float* const* G,
-                                         const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes,
-                                         long long M, int K0, int H, int D, int l2, float p, const unsigned long long* seeds, void* st) {
-    return input_mlp_h_bwd(dout, x, dtype, nullptr, P, G, arena, arena_bytes, flags, tmp, tmp_bytes, M, K0, H, D, l2, p, seeds, st);
-}
-extern "C" int stage_grp_input_mlp_rag_h_fwd(const void* x, int dtype, const int* src_rows, const float* const* P, float* out,
-                                             void* arena, size_t arena_bytes, int* flags, long long M, int K0, int H, int D, int l2,
-                                             float p, const unsigned long long* seeds, void* st) {
-    if (!src_rows) return STAGE_ERR_SHAPE;
-    return input_mlp_h_fwd(x, dtype, src_rows, P, out, arena, arena_bytes, flags, M, K0, H, D, l2, p, seeds, st);
-}
-extern "C" int stage_grp_input_mlp_rag_h_bwd(const float* dout, const void* x, int dtype, const int* src_rows, const float* const* P,
-                                             float* const* G, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
-                                             size_t tmp_bytes, long long M, int K0, int H, int D, int l2, float p,
-                                             const unsigned long long* seeds, void* st) {
-    if (!src_rows) return STAGE_ERR_SHAPE;
-    return input_mlp_h_bwd(dout, x, dtype, src_rows, P, G, arena, arena_bytes, flags, tmp, tmp_bytes, M, K0, H, D, l2, p, seeds, st);
+    return mlp_first_bwd(t.dy0, x, dtype, src_rows, P, G, a, M, K0, l2, p, seeds[0], t.ws, st);
 }
 
 // =====================================================================================================================
@@ -1381,13 +1310,6 @@ extern "C" int stage_grp_pool_cls_bwd_s(const float* d_logits, const float* mask
                            D / 4, slots);
     STAGE_LAUNCH_CHECK();
     return 0;
-}
-extern "C" int stage_grp_pool_cls_bwd(const float* d_logits, const float* mask, const int* idx_g, const int* meta,
-                                      const float* const* P, float* const* G, float* d_first, const void* arena, size_t arena_bytes,
-                                      void* tmp, size_t tmp_bytes, int N, int NA, int Li, int D, long long Pn, float p,
-                                      const unsigned long long* seeds, void* st) {
-    return stage_grp_pool_cls_bwd_s(d_logits, mask, idx_g, meta, P, G, d_first, arena, arena_bytes, tmp, tmp_bytes, N, NA, Li, D, Pn, 2, p,
-                                    seeds, st);
 }
 
 // ---- G7  evaluation head: span of every candidate row + windowed / global pooling + answer classifier (model/stage.py:440-448,

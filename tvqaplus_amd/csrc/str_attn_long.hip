@@ -674,11 +674,9 @@ __global__ __launch_bounds__(256) void lng_frame_nv_kernel(const float* __restri
 
 #define LNG_CHUNKS 8
 
-extern "C" size_t stage_str_attn_long_bwd_ws_bytes(int N, int NA, int Lqa, int D) {
-    return (size_t)LNG_CHUNKS * N * NA * Lqa * D * sizeof(float);
-}
+static size_t lng_part_bytes(int N, int NA, int Lqa, int D) { return (size_t)LNG_CHUNKS * N * NA * Lqa * D * sizeof(float); }
 extern "C" size_t stage_str_attn_long_bwd_qm_ws_bytes(int N, int NA, int Li, int Lqa, int D) {
-    return stage_str_attn_long_bwd_ws_bytes(N, NA, Lqa, D) + (((size_t)N * Li * sizeof(int) + 255) & ~(size_t)255);
+    return lng_part_bytes(N, NA, Lqa, D) + (((size_t)N * Li * sizeof(int) + 255) & ~(size_t)255);
 }
 
 template <typename T>
@@ -706,14 +704,10 @@ static int lng_fwd(const void* Cn, const void* Q, const void* Qn, const float* c
 template <typename T>
 static int lng_bwd(const void* dA, const void* A, const float* ext, const void* Cn, const void* Q, const void* Qn, const float* Sn,
                    float* dS, float* dQraw, float* dQn, float* dCn, int N, int NA, int Li, int Lqa, int Lr, int D, float scale,
-                   float* part, hipStream_t st, const float* qmask = nullptr, int* fnv = nullptr) {
+                   float* part, hipStream_t st, const float* qmask, int* fnv) {
     const int CR = NA * Lqa, CT = (CR + 15) / 16;
-    if (qmask && fnv) {
-        hipLaunchKernelGGL(lng_frame_nv_kernel, dim3((unsigned)(N * Li)), dim3(256), 0, st, qmask, ext, fnv, NA, Li, Lqa, Lr);
-        STAGE_LAUNCH_CHECK();
-    } else {
-        fnv = nullptr;
-    }
+    hipLaunchKernelGGL(lng_frame_nv_kernel, dim3((unsigned)(N * Li)), dim3(256), 0, st, qmask, ext, fnv, NA, Li, Lqa, Lr);
+    STAGE_LAUNCH_CHECK();
     int nchunks = LNG_CHUNKS;
     if (nchunks > Li) nchunks = Li;
     const long items = (long)N * CT * nchunks;
@@ -772,21 +766,7 @@ extern "C" int stage_str_attn_long_fwd(const void* Cn, const void* Q, const void
                         : lng_fwd<float>(Cn, Q, Qn, c_mask, q_mask, A, S_raw, S_norm, N, NA, Li, Lqa, Lr, D, scale, st);
 }
 
-extern "C" int stage_str_attn_long_bwd(const void* dA, const void* A, const float* dS_raw_ext, const void* Cn, const void* Q,
-                                       const void* Qn, const float* S_norm, float* dS_ws, float* dQraw, float* dQn, float* dCn,
-                                       int N, int NA, int Li, int Lqa, int Lr, int D, float scale, int storage_bf16, void* ws,
-                                       size_t ws_bytes, void* stream) {
-    if (N <= 0 || Li <= 0) return 0;
-    if (Lr < 1 || Lqa < 1 || NA < 1) return STAGE_ERR_SHAPE;
-    if (ws_bytes < stage_str_attn_long_bwd_ws_bytes(N, NA, Lqa, D)) return STAGE_ERR_WORKSPACE;
-    hipStream_t st = (hipStream_t)stream;
-    return storage_bf16 ? lng_bwd<__hip_bfloat16>(dA, A, dS_raw_ext, Cn, Q, Qn, S_norm, dS_ws, dQraw, dQn, dCn, N, NA, Li, Lqa, Lr, D,
-                                                  scale, (float*)ws, st)
-                        : lng_bwd<float>(dA, A, dS_raw_ext, Cn, Q, Qn, S_norm, dS_ws, dQraw, dQn, dCn, N, NA, Li, Lqa, Lr, D, scale,
-                                         (float*)ws, st);
-}
-
-// The same with the region mask at hand: region blocks behind a frame's last valid region are skipped (exact zeros) unless the external
+// Backward, with the region mask at hand: region blocks behind a frame's last valid region are skipped (exact zeros) unless the external
 // gradient touches them (lng_frame_nv_kernel).  ws from stage_str_attn_long_bwd_qm_ws_bytes.
 extern "C" int stage_str_attn_long_bwd_qm(const void* dA, const void* A, const float* dS_raw_ext, const void* Cn, const void* Q,
                                           const void* Qn, const float* S_norm, const float* q_mask, float* dS_ws, float* dQraw,
@@ -796,7 +776,7 @@ extern "C" int stage_str_attn_long_bwd_qm(const void* dA, const void* A, const f
     if (Lr < 1 || Lqa < 1 || NA < 1 || !q_mask) return STAGE_ERR_SHAPE;
     if (ws_bytes < stage_str_attn_long_bwd_qm_ws_bytes(N, NA, Li, Lqa, D)) return STAGE_ERR_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    int* fnv = (int*)((char*)ws + stage_str_attn_long_bwd_ws_bytes(N, NA, Lqa, D));
+    int* fnv = (int*)((char*)ws + lng_part_bytes(N, NA, Lqa, D));
     return storage_bf16 ? lng_bwd<__hip_bfloat16>(dA, A, dS_raw_ext, Cn, Q, Qn, S_norm, dS_ws, dQraw, dQn, dCn, N, NA, Li, Lqa, Lr, D,
                                                   scale, (float*)ws, st, q_mask, fnv)
                         : lng_bwd<float>(dA, A, dS_raw_ext, Cn, Q, Qn, S_norm, dS_ws, dQraw, dQn, dCn, N, NA, Li, Lqa, Lr, D, scale,

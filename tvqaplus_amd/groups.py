@@ -186,65 +186,66 @@ def feat16_ok(x) -> bool:
 
 
 def _features(x):
-    """-> (x, dtype code): float32 features (code 0: the fp32 entry points), or half-precision ones as they are (never a copy)."""
+    """-> (x, dtype code): float32 features, or half-precision ones as they are (never a copy)."""
     if x.dtype in _HALF:
         if not feat16_ok(x):
             raise Unsupported("half-precision features: width, alignment or layout")
         return x, _HALF[x.dtype]
-    return _chk(x, "x"), 0
+    return _chk(x, "x"), _lib.STAGE_DT_F32
 
 
 class _InputMLP(torch.autograd.Function):
     @_on_device
-    def forward(ctx, x, l2: int, p: float, seeds, *params):
-        x, half = _features(x)
+    def forward(ctx, x, clay, l2: int, p: float, seeds, *params):
+        x, dtype = _features(x)                # with a layout: the padded (or packed) feature tensor, the rows clay.src_rows of it
         ctx.sinks = _sinks(params)
         params = _params(params)
         K0, H, D = x.shape[-1], params[2].shape[0], params[6].shape[0]
-        M = x.numel() // K0
-        lib = _lib.load()
-        if half:
-            ab = _size("stage_grp_input_mlp_h_arena_bytes", M, K0, H, D)
+        if clay is None:
+            M = cap = x.numel() // K0
+            rows = None
+            out = torch.empty(x.shape[:-1] + (D,), dtype=torch.float32, device=x.device)
         else:
-            ab = _size("stage_grp_input_mlp_arena_bytes", M, K0, H, D, int(l2))
+            M, cap = clay.U, clay.Ucap
+            rows = clay.src_rows.data_ptr()
+            out = _rows(M, D, x.device)
+        ab = _size("stage_grp_input_mlp_arena_bytes", cap, K0, H, D, int(l2), dtype)
         arena = _buf(ab, x.device)
-        out = torch.empty(x.shape[:-1] + (D,), dtype=torch.float32, device=x.device)
         flags = _flags()
-        if half:
-            _rc(lib.stage_grp_input_mlp_h_fwd(x.data_ptr(), half, _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags, M, K0, H, D,
-                                              int(l2), float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_h_fwd")
-        else:
-            _rc(lib.stage_grp_input_mlp_fwd(x.data_ptr(), _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags, M, K0, H, D, int(l2),
-                                            float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_fwd")
+        _rc(_lib.load().stage_grp_input_mlp_fwd(x.data_ptr(), dtype, rows, _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags, M,
+                                                K0, H, D, int(l2), float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_fwd")
         ctx.save_for_backward(x, arena, *params)      # (half-precision features: the caller's tensor itself)
-        ctx.cfg = (M, K0, H, D, int(l2), float(p), tuple(seeds), flags, ab)
-        ctx.half = half
+        ctx.cfg = (dtype, M, cap, K0, H, D, int(l2), float(p), tuple(seeds), flags, ab)
+        ctx.clay = clay
         return out
 
     @_on_device
     def backward(ctx, dout):
         x, arena, *params = ctx.saved_tensors
-        M, K0, H, D, l2, p, seeds, flags, ab = ctx.cfg
+        dtype, M, cap, K0, H, D, l2, p, seeds, flags, ab = ctx.cfg
         dout = _chk(dout, "dout")
-        lib = _lib.load()
         grads = _grad_views(params)
-        tb = _size("stage_grp_input_mlp_bwd_tmp_bytes", M, K0, H, D)
+        tb = _size("stage_grp_input_mlp_bwd_tmp_bytes", cap, K0, H, D)
         tmp = _buf(tb, x.device)
-        if ctx.half:
-            _rc(lib.stage_grp_input_mlp_h_bwd(dout.data_ptr(), x.data_ptr(), ctx.half, _ptrs(params), _ptrs(grads), arena.data_ptr(), ab,
-                                              flags, tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()),
-                "stage_grp_input_mlp_h_bwd")
-        else:
-            _rc(lib.stage_grp_input_mlp_bwd(dout.data_ptr(), x.data_ptr(), _ptrs(params), _ptrs(grads), arena.data_ptr(), ab, flags,
-                                            tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()), "stage_grp_input_mlp_bwd")
-        return (None, None, None, None) + _deliver(ctx.sinks, grads)
+        rows = None if ctx.clay is None else ctx.clay.src_rows.data_ptr()
+        _rc(_lib.load().stage_grp_input_mlp_bwd(dout.data_ptr(), x.data_ptr(), dtype, rows, _ptrs(params), _ptrs(grads), arena.data_ptr(),
+                                                ab, flags, tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()),
+            "stage_grp_input_mlp_bwd")
+        return (None, None, None, None, None) + _deliver(ctx.sinks, grads)
 
 
 def input_mlp(x, l2: bool, p: float, seeds, params):
     """x (..., K0) features -> (..., D).  params: ln0.w ln0.b fc1.w fc1.b ln1.w ln1.b fc2.w fc2.b ln2.w ln2.b.
     x: float32, or float16 / bfloat16 that ``feat16_ok`` accepts -- read in place and converted in registers (csrc/feat16.hip): the
     result is that of ``x.float()``, no fp32 copy of the features exists, and the backward re-reads the same tensor."""
-    return _InputMLP.apply(x, int(bool(l2)), p, tuple(seeds), *params)
+    return _InputMLP.apply(x, None, int(bool(l2)), p, tuple(seeds), *params)
+
+
+def input_mlp_rag(x, clay, l2: bool, p: float, seeds, params):
+    """As ``input_mlp`` on the compact rows of a ragged context stream: x the padded (..., K0) features, ``clay.src_rows`` the rows of it
+    that exist; -> (clay.U, D).  Half-precision x: as ``input_mlp``.  A packed stream (tvqaplus_amd/packed.py) hands over its
+    ``(P + 1, K0)`` rows instead: the layout's source rows then point into that buffer, its zero row included."""
+    return _InputMLP.apply(x, clay, int(bool(l2)), p, tuple(seeds), *params)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -466,62 +467,6 @@ def encoder_block_rag(x, pe, qa_mask, lay, k: int, p: float, seeds, params):
     (example, candidate, frame) (model/stage.py:502-503); qa_mask (N*NA, Lqa).  qa_mask None: no pooling, (U, D) comes back -- an
     encoder block over the ragged sequences of a context stream (``lay`` a ``ragged.CtxLayout``)."""
     return _EncoderRag.apply(x, pe, qa_mask, lay, k, p, tuple(seeds), *params)
-
-
-class _InputMLPRag(torch.autograd.Function):
-    @_on_device
-    def forward(ctx, x, clay, l2: int, p: float, seeds, *params):
-        x, half = _features(x)                 # the padded feature tensor, (..., K0)
-        ctx.sinks = _sinks(params)
-        params = _params(params)
-        K0, H, D = x.shape[-1], params[2].shape[0], params[6].shape[0]
-        M = clay.U
-        lib = _lib.load()
-        if half:
-            ab = _size("stage_grp_input_mlp_h_arena_bytes", clay.Ucap, K0, H, D)
-        else:
-            ab = _size("stage_grp_input_mlp_arena_bytes", clay.Ucap, K0, H, D, int(l2))
-        arena = _buf(ab, x.device)
-        out = _rows(M, D, x.device)
-        flags = _flags()
-        if half:
-            _rc(lib.stage_grp_input_mlp_rag_h_fwd(x.data_ptr(), half, clay.src_rows.data_ptr(), _ptrs(params), out.data_ptr(), arena.data_ptr(),
-                                                  ab, flags, M, K0, H, D, int(l2), float(p), _u64(seeds), _stream()),
-                "stage_grp_input_mlp_rag_h_fwd")
-        else:
-            _rc(lib.stage_grp_input_mlp_rag_fwd(x.data_ptr(), clay.src_rows.data_ptr(), _ptrs(params), out.data_ptr(), arena.data_ptr(), ab, flags,
-                                                M, K0, H, D, int(l2), float(p), _u64(seeds), _stream()), "stage_grp_input_mlp_rag_fwd")
-        ctx.save_for_backward(x, arena, *params)
-        ctx.cfg = (M, K0, H, D, int(l2), float(p), tuple(seeds), flags, ab)
-        ctx.clay = clay
-        ctx.half = half
-        return out
-
-    @_on_device
-    def backward(ctx, dout):
-        x, arena, *params = ctx.saved_tensors
-        M, K0, H, D, l2, p, seeds, flags, ab = ctx.cfg
-        dout = _chk(dout, "dout")
-        lib = _lib.load()
-        grads = _grad_views(params)
-        tb = _size("stage_grp_input_mlp_bwd_tmp_bytes", ctx.clay.Ucap, K0, H, D)
-        tmp = _buf(tb, x.device)
-        if ctx.half:
-            _rc(lib.stage_grp_input_mlp_rag_h_bwd(dout.data_ptr(), x.data_ptr(), ctx.half, ctx.clay.src_rows.data_ptr(), _ptrs(params),
-                                                  _ptrs(grads), arena.data_ptr(), ab, flags, tmp.data_ptr(), tb, M, K0, H, D, l2, p,
-                                                  _u64(seeds), _stream()), "stage_grp_input_mlp_rag_h_bwd")
-        else:
-            _rc(lib.stage_grp_input_mlp_rag_bwd(dout.data_ptr(), x.data_ptr(), ctx.clay.src_rows.data_ptr(), _ptrs(params), _ptrs(grads),
-                                                arena.data_ptr(), ab, flags, tmp.data_ptr(), tb, M, K0, H, D, l2, p, _u64(seeds), _stream()),
-                "stage_grp_input_mlp_rag_bwd")
-        return (None, None, None, None, None) + _deliver(ctx.sinks, grads)
-
-
-def input_mlp_rag(x, clay, l2: bool, p: float, seeds, params):
-    """As ``input_mlp`` on the compact rows of a ragged context stream: x the padded (..., K0) features, ``clay.src_rows`` the rows of it
-    that exist; -> (clay.U, D).  Half-precision x: as ``input_mlp``.  A packed stream (tvqaplus_amd/packed.py) hands over its
-    ``(P + 1, K0)`` rows instead: the layout's source rows then point into that buffer, its zero row included."""
-    return _InputMLPRag.apply(x, clay, int(bool(l2)), p, tuple(seeds), *params)
 
 
 # ---------------------------------------------------------------------------------------------------------------

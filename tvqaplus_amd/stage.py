@@ -550,14 +550,17 @@ class STAGE(nn.Module):
             M, L, _ = data.shape
         else:
             L = clay.Lqa       # (a packed stream hands its (P + 1, K) rows over: the padded row length is the layout's)
+
+        def mlp_params():
+            return [self._g(w) for w in (init_encoder[0].weight, init_encoder[0].bias, init_encoder[2].weight, init_encoder[2].bias,
+                                         init_encoder[4].weight, init_encoder[4].bias, downsize_encoder[1].weight,
+                                         downsize_encoder[1].bias, downsize_encoder[3].weight, downsize_encoder[3].bias)]
+
         if clay is not None:
             # ragged context rows (tvqaplus_amd/ragged.py: CtxLayout): the MLP reads the live rows of the padded features in place
             # (of a packed stream: its rows and its zero row, through the same table), everything behind it -- and the attention --
             # runs on the compact rows
-            params = [init_encoder[0].weight, init_encoder[0].bias, init_encoder[2].weight, init_encoder[2].bias,
-                      init_encoder[4].weight, init_encoder[4].bias, downsize_encoder[1].weight, downsize_encoder[1].bias,
-                      downsize_encoder[3].weight, downsize_encoder[3].bias]
-            y = groups.input_mlp_rag(data, clay, l2_normalize, self._p(), self._seeds(2), [self._g(w) for w in params])
+            y = groups.input_mlp_rag(data, clay, l2_normalize, self._p(), self._seeds(2), mlp_params())
             if clay.tab.halo >= L:
                 # whole frames (self-attention in the input encoder): S sequences of L positions, the ordinary encoder path
                 mc = data_mask.index_select(0, clay.live_frames.long()).contiguous()
@@ -568,26 +571,17 @@ class STAGE(nn.Module):
                 y = groups.encoder_block_rag(y, blk.position_encoding.rows(L), None, clay, k, self._p(),
                                              self._seeds((blk.n_conv + 1) // 2), [self._g(w) for w in bp])
             return y
-        if (feat16 and data.dtype in (torch.float16, torch.bfloat16) and self._grouped() and not self.fuse_input_ln
-                and groups.feat16_ok(data)):
-            # half-precision features, fp32 model: converted in registers by the group's first kernel -- no fp32 copy to keep alive
-            params = [init_encoder[0].weight, init_encoder[0].bias, init_encoder[2].weight, init_encoder[2].bias,
-                      init_encoder[4].weight, init_encoder[4].bias, downsize_encoder[1].weight, downsize_encoder[1].bias,
-                      downsize_encoder[3].weight, downsize_encoder[3].bias]
-            params = [self._g(w) for w in params]
-            y = self._try_group(lambda seeds: groups.input_mlp(data, l2_normalize, self._p(), seeds, params), 2)
-            if y is not None:
-                return self._stacked_encoder(y.view(M, L, -1), data_mask, input_encoder)
-        if data.dtype != self.storage:
-            data = data.to(self.storage)      # bf16 storage: features are rounded once on entry
-        if self._grouped() and not self.fuse_input_ln and data.dtype == torch.float32:
-            params = [init_encoder[0].weight, init_encoder[0].bias, init_encoder[2].weight, init_encoder[2].bias,
-                      init_encoder[4].weight, init_encoder[4].bias, downsize_encoder[1].weight, downsize_encoder[1].bias,
-                      downsize_encoder[3].weight, downsize_encoder[3].bias]
-            params = [self._g(w) for w in params]
-            y = self._try_group(lambda seeds: groups.input_mlp(data, l2_normalize, self._p(), seeds, params), 2)
-            if y is not None:
-                return self._stacked_encoder(y.view(M, L, -1), data_mask, input_encoder)
+        grouped = self._grouped() and not self.fuse_input_ln
+        # half-precision features, fp32 model: tried as they are (converted in registers by the group's first kernel -- no fp32 copy to
+        # keep alive); when the group declines them, or for any other features: upcast, then the group on the fp32 rows
+        half = feat16 and grouped and data.dtype in (torch.float16, torch.bfloat16) and groups.feat16_ok(data)
+        for as_is in (True, False) if half else (False,):
+            if not as_is and data.dtype != self.storage:
+                data = data.to(self.storage)      # bf16 storage: features are rounded once on entry
+            if grouped and (as_is or data.dtype == torch.float32):
+                y = self._try_group(lambda seeds: groups.input_mlp(data, l2_normalize, self._p(), seeds, mlp_params()), 2)
+                if y is not None:
+                    return self._stacked_encoder(y.view(M, L, -1), data_mask, input_encoder)
         if l2_normalize:
             data = ops.l2norm(data)
         if self.fuse_input_ln and ops.input_ln_linear_supported(data, init_encoder[2].weight):
@@ -962,7 +956,7 @@ class STAGE(nn.Module):
         if N * NA * li_any * Lqa < self.ragged_min_rows:
             return none
         if D != 128 or not (4 <= Lqa <= 40) or self.bridge_hsz % 4 or self.bridge_hsz > 1024:
-            return none          # (the ragged input-MLP group's own limits: stage_grp_input_mlp_rag_fwd declines other widths)
+            return none          # (the ragged input-MLP group's own limits: stage_grp_input_mlp_fwd declines other widths)
         # words kept behind the last valid one: the classifier encoder's convolution halo -- or every word of a live frame when that
         # encoder is not a single conv-only block (self-attention mixes all words; the frames that are dead are still skipped)
         cls_halo = Lqa
