@@ -27,7 +27,7 @@ extern "C" {
 #define STAGE_ERR_WORKSPACE (-2)  /* workspace too small */
 
 /* ---- library info -------------------------------------------------------------------------------------------- */
-#define STAGE_HIP_ABI_VERSION 6   /* what stage_hip_abi_version() of a matching library returns; bumped when an existing symbol's signature or meaning changes (added symbols keep it) */
+#define STAGE_HIP_ABI_VERSION 7  /* what stage_hip_abi_version() of a matching library returns; bumped when an existing symbol's signature or meaning changes (added symbols keep it) */
 int stage_hip_abi_version(void);
 const char* stage_hip_error_string(int code);
 /* Measurement helpers (bench.py; no reference counterpart): events for hosts without a HIP binding, and a one-shot hook that makes the
@@ -375,18 +375,30 @@ int stage_grp_input_mlp_bwd(const float* dout, const void* x, int dtype, const i
                             float* const* grads, const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes,
                             long long M, int K0, int H, int D, int l2, float p_drop, const unsigned long long* seeds, void* stream);
 /* G2 encoder block without self-attention (model/encoder.py:29-52, model/cnn.py:37-47, model/position_encoding.py:38-43):
- * x (M, L, D), pe (>= L, D).  pool_mask (M, L) != NULL: out = masked max over L of the block's output (model/stage.py:503),
- * (M, D); otherwise out (M, L, D).  params / grads: per conv i (ln_g ln_b dw_w dw_b pw_w pw_b), then final_g final_b;
- * seeds: one per even conv index.  dx may be NULL.                                                                        */
-size_t stage_grp_encoder_arena_bytes(long long M, int L, int D, int n_conv, int pooled);
+ * `rows` rows of x that form S sequences of at most L positions, pe (>= L, D).  pool_mask != NULL: out = masked max over each
+ * sequence of the block's output (model/stage.py:503); otherwise out (rows, D).  params / grads: per conv i (ln_g ln_b dw_w dw_b
+ * pw_w pw_b), then final_g final_b; seeds: one per even conv index; flags[n_conv + 1].  dx (rows, D) may be NULL.
+ * One entry point per direction; the forms differ in the LayerNorm -> depthwise-conv launch and in the final stage only:
+ *   T == NULL  dense: x (S, L, D); rows = S * L and cap = rows (anything else: STAGE_ERR_SHAPE); pool_mask (S, L); a pooled out is
+ *              (S, D) and out_rows is ignored; n_conv 0..8.
+ *   T != NULL  ragged ("K-groups on ragged rows" below): x (rows, D) = the U compact rows of the S sequences T[2] = seq names, L = the
+ *              longest (Lqa); cap = Ucap >= rows, the row count the arena is sized for; pool_mask = qa_mask (groups, L), a pooled out
+ *              is (out_rows, D) dense -- rows no sequence writes come back filled -- and the backward reads T[3] = rowinfo;
+ *              unpooled: out (rows, D), out_rows is ignored; n_conv 1..8; pooled needs D = 128.
+ * Size queries: cap and out_rows as above (dense: out_rows = S), ragged = (T != NULL), pooled = (pool_mask != NULL).
+ * Refused before a launch, forward and backward, with STAGE_ERR_SHAPE: S <= 0, L < 1, rows <= 0, n_conv outside the form's range, a
+ * (D, k) the LayerNorm -> depthwise-conv kernels do not take, D > 1024, and the form's conditions above.  A buffer smaller than its
+ * query names: STAGE_ERR_WORKSPACE.                                                                                              */
+size_t stage_grp_encoder_arena_bytes(long long cap, long long out_rows, int D, int n_conv, int pooled, int ragged);
 int stage_grp_encoder_fwd(const float* x, const float* pe, const float* pool_mask, const float* const* params, float* out,
-                          void* arena, size_t arena_bytes, int* flags, long long M, int L, int D, int n_conv, int k, float p_drop,
-                          const unsigned long long* seeds, void* stream);
-size_t stage_grp_encoder_bwd_tmp_bytes(long long M, int L, int D, int k, int pooled);
-int stage_grp_encoder_bwd(const float* dout, const float* x, const float* pool_mask, const float* const* params,
-                          float* const* grads, float* dx, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
-                          size_t tmp_bytes, long long M, int L, int D, int n_conv, int k, float p_drop,
-                          const unsigned long long* seeds, void* stream);
+                          const int* const* T, void* arena, size_t arena_bytes, int* flags, long long rows, long long cap, long long S,
+                          long long out_rows, int L, int D, int n_conv, int k, float p_drop, const unsigned long long* seeds,
+                          void* stream);
+size_t stage_grp_encoder_bwd_tmp_bytes(long long cap, int D, int k, int pooled, int ragged);
+int stage_grp_encoder_bwd(const float* dout, const float* pool_mask, const float* const* params, float* const* grads, float* dx,
+                          const int* const* T, const void* arena, size_t arena_bytes, const int* flags, void* tmp, size_t tmp_bytes,
+                          long long rows, long long cap, long long S, long long out_rows, int L, int D, int n_conv, int k,
+                          float p_drop, const unsigned long long* seeds, void* stream);
 /* G3 QA <-> context attention + down-projection (model/stage.py:365-387): qa (N,NA,Lqa,D), ctx (N,Li,Lr,D) ->
  * mixed (N,NA,Li,Lqa,D), S_raw / S_norm (N,NA,Li,Lqa,Lr).  params / grads: ln_g ln_b W c; seeds[3] = context-side, region-side,
  * LayerNorm dropout.  Backward: dS_ext = gradient on S_raw or NULL; d_qa sums both uses of the QA embedding.              */
@@ -652,7 +664,7 @@ int stage_ln_masked_max_rag_bwd(const float* dout, const int* argmax, const floa
                                 const int* rowinfo, long long rows, int K, void* ws, size_t ws_bytes, void* stream);
 /* K-groups on ragged rows (csrc/groups.hip "RAGGED TOKEN ROWS"): T = host array of the device tables fmap, gdesc, seq, rowinfo, cq
  * (cq NULL: dense context stream; Uc = rows of ctx / d_ctx) and -- the qa_ctx group, 6 entries -- wtab (the balanced work table of
- * stage_cat3_dx_ln_bwd_rag, or NULL).  The encoder group pools when qa_mask != NULL, else returns (U, D). */
+ * stage_cat3_dx_ln_bwd_rag, or NULL).  The encoder group on these rows: stage_grp_encoder_* above with T != NULL. */
 int stage_grp_qa_ctx_rag_supported(int N, int NA, int Li, int Lqa, int Lr, int D, long long U, long long Fc);
 size_t stage_grp_qa_ctx_rag_arena_bytes(int N, int NA, int Lqa, int D, long long Ucap, long long Fc);
 size_t stage_grp_qa_ctx_rag_bwd_tmp_bytes(int N, int NA, int Li, int Lqa, int Lr, int D, long long Ucap, long long Uc);
@@ -666,16 +678,6 @@ int stage_grp_qa_ctx_rag_bwd(const float* d_mixed, const float* dS_ext, const fl
                              float* d_ctx, const int* const* T, void* arena, size_t arena_bytes, const int* flags, void* tmp,
                              size_t tmp_bytes, int N, int NA, int Li, int Lqa, int Lr, int D, long long U, long long Ucap,
                              long long Fc, long long Uc, float scale, float p, const unsigned long long* seeds, void* stream);
-size_t stage_grp_encoder_rag_arena_bytes(long long Ucap, long long Rd, int D, int n_conv);
-size_t stage_grp_encoder_rag_bwd_tmp_bytes(long long Ucap, int D, int k);
-int stage_grp_encoder_rag_fwd(const float* x, const float* pe, const float* qa_mask, const float* const* P, float* out,
-                              const int* const* T, void* arena, size_t arena_bytes, int* flags, long long U, long long Ucap,
-                              long long S, long long Rd, int Lqa, int D, int n_conv, int k, float p,
-                              const unsigned long long* seeds, void* stream);
-int stage_grp_encoder_rag_bwd(const float* dout, const float* qa_mask, const float* const* P, float* const* Gr, float* dx,
-                              const int* const* T, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
-                              size_t tmp_bytes, long long U, long long Ucap, long long S, long long Rd, int Lqa, int D, int n_conv,
-                              int k, float p, const unsigned long long* seeds, void* stream);
 
 /* ---- Flat Adam (main.py:63-66: clip_grad_norm_(model.parameters(), 10) + optimizer.step() with torch.optim.Adam) ----------------
  * The clip and the Adam update on the packed gradient buffer (csrc/flat_adam.hip; tvqaplus_amd/optim.py: FlatAdam): ONE call, two

@@ -111,4 +111,4 @@ def test_score_row_symbols_answer_without_a_gpu():
         assert name in _lib.SIGNATURES and hasattr(lib, name)
     assert [lib.stage_score_rows_supported(v) for v in (1, 20, 64, 0, 65)] == [1, 1, 1, 0, 0]
     assert groups.score_rows_supported(20) and not groups.score_rows_supported(65)
-    assert lib.stage_hip_abi_version() == 6
+    assert lib.stage_hip_abi_version() == 7

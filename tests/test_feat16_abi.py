@@ -29,7 +29,7 @@ def test_symbols_exported_and_bound(lib):
     assert (_lib.STAGE_DT_F32, _lib.STAGE_DT_F16, _lib.STAGE_DT_BF16) == (F32, F16, BF16)
     hdr = open(os.path.join(ROOT, "include", "stage_hip.h")).read()
     assert "#define STAGE_DT_F32 0" in hdr and "#define STAGE_DT_F16 1" in hdr and "#define STAGE_DT_BF16 2" in hdr
-    assert lib.stage_hip_abi_version() == 6
+    assert lib.stage_hip_abi_version() == 7
 
 
 def test_supported_truth_table(lib):

@@ -28,7 +28,7 @@ def test_symbols_exported_and_bound_under_abi_5(lib):
         assert name in _lib.SIGNATURES, name
         fn = getattr(lib, name)
         assert fn.argtypes == _lib.SIGNATURES[name][1] and fn.restype is _lib.SIGNATURES[name][0], name
-    assert lib.stage_hip_abi_version() == 6 == _lib.ABI_VERSION
+    assert lib.stage_hip_abi_version() == 7 == _lib.ABI_VERSION
 
 
 def test_workspace_query_needs_no_gpu(lib):

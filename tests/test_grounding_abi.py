@@ -36,7 +36,7 @@ def test_header_binding_and_exports_agree_under_abi_5(lib):
         assert argtypes == args and res is kinds[m.group(1)], name
         fn = getattr(lib, name)
         assert fn.argtypes == argtypes and fn.restype is res, name
-    assert lib.stage_hip_abi_version() == 6 == _lib.ABI_VERSION
+    assert lib.stage_hip_abi_version() == 7 == _lib.ABI_VERSION
 
 
 def test_queries_need_no_gpu(lib):

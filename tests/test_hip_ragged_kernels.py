@@ -6,7 +6,7 @@ What runs on ragged rows (tvqaplus_amd/ragged.py, docs/ragged.md) and was only e
 * csrc/rowops.hip       stage_layernorm_gather_fwd/bwd, stage_l2norm_gather_fwd           -- fp64 on the gathered rows
 * csrc/ln_dwconv.hip    stage_ln_dwconv_rag_fwd/bwd                                       -- fp64, each sequence alone
 * csrc/rowops.hip       stage_ln_masked_max_rag_fwd/bwd                                   -- fp64, each sequence alone, first maximum wins
-* csrc/groups.hip       stage_grp_encoder_rag_fwd/bwd (groups.encoder_block_rag)          -- oracle.encoder_block in fp64, each sequence alone
+* csrc/groups.hip       stage_grp_encoder_fwd/bwd with tables (groups.encoder_block_rag)  -- oracle.encoder_block in fp64, each sequence alone
 
 The reference of every ``seq`` table cuts the rows [start, start + len) of a sequence out and evaluates plain torch in float64 on them
 (F.layer_norm, F.conv1d with zero padding at the sequence's OWN ends, oracle.mask_logits, oracle.encoder_block), so a halo row read

@@ -158,7 +158,7 @@ def test_symbols_exported_and_bound(lib):
         assert name in _lib.SIGNATURES, name
     hdr = open(os.path.join(ROOT, "include", "stage_hip.h")).read()
     assert all(("int %s(" % name) in hdr for name in SYMBOLS)
-    assert lib.stage_hip_abi_version() == 6
+    assert lib.stage_hip_abi_version() == 7
 
 
 def test_bad_shapes_are_refused_before_any_launch(lib):

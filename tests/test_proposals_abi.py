@@ -109,7 +109,7 @@ def test_symbol_in_header_binding_and_library():
     lib = _lib.load()
     assert hasattr(lib, "stage_proposal_meta")
     hdr = open(HEADER).read()
-    assert int(re.search(r"#define STAGE_HIP_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == lib.stage_hip_abi_version() == 6
+    assert int(re.search(r"#define STAGE_HIP_ABI_VERSION (\d+)", hdr).group(1)) == _lib.ABI_VERSION == lib.stage_hip_abi_version() == 7
 
 
 def test_shape_limits_are_answered_before_any_launch():

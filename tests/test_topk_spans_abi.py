@@ -35,7 +35,7 @@ def test_new_symbols_in_header_binding_and_library():
     assert _lib.SIGNATURES["stage_topk_spans"] == (I, [P, I, P, P, LL, I, I, P])
     SZ = _lib.SZ
     assert _lib.SIGNATURES["stage_grp_pool_cls_bwd_s"] == (I, [P, P, P, P, P, P, P, P, SZ, P, SZ, I, I, I, I, LL, I, F, P, P])    # `slots` behind P
-    assert int(re.search(r"#define STAGE_HIP_ABI_VERSION (\d+)", hdr).group(1)) == 6 == _lib.ABI_VERSION == lib.stage_hip_abi_version()
+    assert int(re.search(r"#define STAGE_HIP_ABI_VERSION (\d+)", hdr).group(1)) == 7 == _lib.ABI_VERSION == lib.stage_hip_abi_version()
     assert int(re.search(r"#define STAGE_TOPK_MAX (\d+)", hdr).group(1)) == 8 == _lib.STAGE_TOPK_MAX
 
 

@@ -107,10 +107,10 @@ SIGNATURES = {
     "stage_grp_input_mlp_fwd": (I, [P, I, P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
     "stage_grp_input_mlp_bwd_tmp_bytes": (SZ, [LL, I, I, I]),
     "stage_grp_input_mlp_bwd": (I, [P, P, I, P, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
-    "stage_grp_encoder_arena_bytes": (SZ, [LL, I, I, I, I]),
-    "stage_grp_encoder_fwd": (I, [P, P, P, P, P, P, SZ, P, LL, I, I, I, I, F, P, P]),
+    "stage_grp_encoder_arena_bytes": (SZ, [LL, LL, I, I, I, I]),
+    "stage_grp_encoder_fwd": (I, [P, P, P, P, P, P, P, SZ, P, LL, LL, LL, LL, I, I, I, I, F, P, P]),
     "stage_grp_encoder_bwd_tmp_bytes": (SZ, [LL, I, I, I, I]),
-    "stage_grp_encoder_bwd": (I, [P, P, P, P, P, P, P, SZ, P, P, SZ, LL, I, I, I, I, F, P, P]),
+    "stage_grp_encoder_bwd": (I, [P, P, P, P, P, P, P, SZ, P, P, SZ, LL, LL, LL, LL, I, I, I, I, F, P, P]),
     "stage_grp_qa_ctx_arena_bytes": (SZ, [I, I, I, I, I]),
     "stage_grp_qa_ctx_fwd": (I, [P, P, P, P, P, P, P, P, P, SZ, P, I, I, I, I, I, I, F, F, P, P]),
     "stage_grp_qa_ctx_bwd_tmp_bytes": (SZ, [I, I, I, I, I, I]),
@@ -187,10 +187,6 @@ SIGNATURES = {
     "stage_grp_qa_ctx_rag_bwd_tmp_bytes": (SZ, [I, I, I, I, I, I, LL, LL]),
     "stage_grp_qa_ctx_rag_fwd": (I, [P, P, P, P, P, P, P, P, P, P, SZ, P, I, I, I, I, I, I, LL, LL, LL, LL, F, F, P, P]),
     "stage_grp_qa_ctx_rag_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, SZ, P, P, SZ, I, I, I, I, I, I, LL, LL, LL, LL, F, F, P, P]),
-    "stage_grp_encoder_rag_arena_bytes": (SZ, [LL, LL, I, I]),
-    "stage_grp_encoder_rag_bwd_tmp_bytes": (SZ, [LL, I, I]),
-    "stage_grp_encoder_rag_fwd": (I, [P, P, P, P, P, P, P, SZ, P, LL, LL, LL, LL, I, I, I, I, F, P, P]),
-    "stage_grp_encoder_rag_bwd": (I, [P, P, P, P, P, P, P, SZ, P, P, SZ, LL, LL, LL, LL, I, I, I, I, F, P, P]),
     # clip + Adam on the packed gradient buffer (csrc/flat_adam.hip; tvqaplus_amd/optim.py): betas is a HOST array of two doubles
     "stage_flat_adam_ws_bytes": (SZ, [LL]),
     "stage_flat_adam_step": (I, [P, P, P, P, I, P, I, P, P, LL, F, P, F, F, F, P, SZ, P, P]),
@@ -207,7 +203,7 @@ SIGNATURES = {
     "stage_grounding_update": (I, [P, LL, P, LL, P, LL, P, I, P, LL, P, LL, I, I, F, F, P]),
 }
 
-ABI_VERSION = 6    # include/stage_hip.h: STAGE_HIP_ABI_VERSION (tests/test_abi.py holds the two together)
+ABI_VERSION = 7   # include/stage_hip.h: STAGE_HIP_ABI_VERSION (tests/test_abi.py holds the two together)
 
 _lib = None
 

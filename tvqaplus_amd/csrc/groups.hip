@@ -230,10 +230,15 @@ extern "C" int stage_grp_input_mlp_bwd(const float* dout, const void* x, int dty
 // =====================================================================================================================
 // G2  encoder block without self-attention (model/encoder.py:29-52, model/cnn.py:37-47, model/position_encoding.py:38-43):
 //     x + pe -> n_conv x [LN (+dropout on even i) -> depthwise conv -> 1x1 conv + ReLU -> + residual] -> final LN
-//     pooled != 0: the caller only needs the masked max over L of the output (model/stage.py:503) -> out (M, D)
+//     pool_mask != NULL: the caller only needs the masked max over the sequence of the output (model/stage.py:503)
 //     params: per conv i: ln_g ln_b dw_w dw_b pw_w pw_b ; then final_g final_b.  seeds: one per even conv index.
 //     flags: [pw mask of conv i] for i < n_conv ; flags[n_conv] = 1 when LayerNorm + max ran fused
 //     Residual adds are deferred into the next LayerNorm's prologue (exported sums), as in STAGE._encoder_block.
+//     One body per direction over `rows` rows that form S sequences; only the LN -> dwconv launch and the final stage have forms:
+//       T == NULL  dense: x (S, L, D), rows = cap = S * L, pool_mask (S, L), a pooled out is (S, D); n_conv >= 0
+//       T != NULL  ragged (tables: "RAGGED TOKEN ROWS" below): x (rows, D) compact = the S sequences of T[2], each at most L long,
+//                  in an arena sized for cap >= rows; pool_mask = qa_mask (groups, L), a pooled out is (out_rows, D) dense, filled
+//                  where no sequence writes; T[3] = rowinfo for the pooled backward; n_conv >= 1
 // =====================================================================================================================
 namespace {
 constexpr int ENC_MAX_CONV = 8;
@@ -244,126 +249,149 @@ struct EncArena {
     int* idx;
     size_t bytes;
 };
-EncArena enc_layout(void* base, long long M, int L, int D, int n_conv, int pooled) {
+EncArena enc_layout(void* base, long long cap, long long out_rows, int D, int n_conv, int pooled, int ragged) {
     Bump b{(char*)base, 0};
     EncArena a;
-    const size_t R = (size_t)M * L;
+    const size_t R = (size_t)cap;
     for (int i = 0; i < n_conv; i++) {
         a.h[i] = b.take<float>(R * D);
         a.s[i] = b.take<float>(R * D);
         a.mean[i] = b.take<float>(R);
         a.rstd[i] = b.take<float>(R);
         a.g[i] = b.take<float>(R * D);
-        a.mask[i] = b.take<unsigned>(lin_mask_words((long long)R, D));
+        a.mask[i] = b.take<unsigned>(lin_mask_words(cap, D));
     }
     a.sf = b.take<float>(R * D);
     a.meanf = b.take<float>(R);
     a.rstdf = b.take<float>(R);
-    a.yf = pooled ? b.take<float>(R * D) : nullptr;          // only used when LayerNorm + max do not run fused
-    a.idx = pooled ? b.take<int>((size_t)M * D) : nullptr;
+    a.yf = pooled && !ragged ? b.take<float>(R * D) : nullptr;   // only used when LayerNorm + max do not run fused (dense only)
+    // (the ragged form carves idx unpooled too, with no entries: its arena ends on a 256-byte boundary, the dense unpooled one does not)
+    a.idx = pooled || ragged ? b.take<int>(pooled ? (size_t)out_rows * D : 0) : nullptr;
     a.bytes = b.off;
     return a;
 }
-}  // namespace
-
-extern "C" size_t stage_grp_encoder_arena_bytes(long long M, int L, int D, int n_conv, int pooled) {
-    if (n_conv > ENC_MAX_CONV) return 0;
-    return enc_layout(nullptr, M, L, D, n_conv, pooled).bytes;
-}
-
-extern "C" int stage_grp_encoder_fwd(const float* x, const float* pe, const float* pool_mask, const float* const* P, float* out,
-                                     void* arena, size_t arena_bytes, int* flags, long long M, int L, int D, int n_conv, int k,
-                                     float p, const unsigned long long* seeds, void* st) {
-    if (M <= 0 || L <= 0 || n_conv < 0 || n_conv > ENC_MAX_CONV || !ln_dwconv_ok(D, k) || D > 1024) return STAGE_ERR_SHAPE;
-    const int pooled = pool_mask != nullptr;
-    EncArena a = enc_layout(arena, M, L, D, n_conv, pooled);
-    if (arena_bytes < a.bytes) return STAGE_ERR_WORKSPACE;
-    const long long R = M * L;
-    const float* pending = x;
-    const float* cur = pe;
-    int period = L;
-    for (int i = 0; i < n_conv; i++) {
-        const float* const* Q = P + 6 * i;
-        const bool drop = (i % 2) == 0;
-        const unsigned long long seed = drop ? seeds[i / 2] : 0ull;
-        TRY(stage_ln_dwconv_fwd(pending, cur, period, a.s[i], Q[0], Q[1], Q[2], Q[3], a.h[i], a.mean[i], a.rstd[i], M, L, D, k, EPS_LN,
-                                drop ? p : 0.f, seed, st));
-        cur = a.s[i];
-        period = 0;
-        TRY(lin_fwd(a.h[i], Q[4], Q[5], a.g[i], a.mask[i], &flags[i], R, D, D, 1, st));
-        pending = a.g[i];
-    }
-    const float* const* F = P + 6 * n_conv;
-    flags[n_conv] = 0;
-    if (pooled && period == 0 && stage_ln_masked_max_supported(L, D)) {
-        flags[n_conv] = 1;
-        return stage_ln_masked_max_fwd(pending, cur, a.sf, F[0], F[1], pool_mask, out, a.idx, a.meanf, a.rstdf, M, L, D, EPS_LN, st);
-    }
-    float* y = pooled ? a.yf : out;
-    TRY(stage_layernorm_fwd(pending, cur, period, a.sf, F[0], F[1], y, a.meanf, a.rstdf, R, D, EPS_LN, 0.f, 0ull, st));
-    if (pooled) TRY(stage_masked_max_fwd(y, pool_mask, nullptr, out, a.idx, M, L, D, st));
-    return 0;
-}
-
-namespace {
 struct EncTmp { float *Ga, *Gb, *dh, *dyf, *wt; void* ws; size_t wsb, bytes; };
-EncTmp enc_tmp(void* base, long long M, int L, int D, int k, int pooled) {
+EncTmp enc_tmp(void* base, long long cap, int D, int k, int pooled, int ragged) {
     Bump b{(char*)base, 0};
     EncTmp t;
-    const size_t R = (size_t)M * L;
+    const size_t R = (size_t)cap;
     t.Ga = b.take<float>(R * D);
     t.Gb = b.take<float>(R * D);
     t.dh = b.take<float>(R * D);
-    t.dyf = pooled ? b.take<float>(R * D) : nullptr;
+    t.dyf = pooled && !ragged ? b.take<float>(R * D) : nullptr;
     t.wt = b.take<float>((size_t)D * D);
-    t.wsb = umax(umax(stage_ln_bwd_ws_bytes(D), stage_ln_dwconv_bwd_ws_bytes(D, k)), lin_bwd_ws((long long)R, D, D));
+    t.wsb = umax(umax(stage_ln_bwd_ws_bytes(D), stage_ln_dwconv_bwd_ws_bytes(D, k)), lin_bwd_ws(cap, D, D));
     t.ws = b.take<char>(t.wsb);
     t.bytes = b.off;
     return t;
 }
-}  // namespace
-
-extern "C" size_t stage_grp_encoder_bwd_tmp_bytes(long long M, int L, int D, int k, int pooled) {
-    return enc_tmp(nullptr, M, L, D, k, pooled).bytes;
+// what each form refuses before a launch
+bool enc_ok(bool ragged, bool pooled, long long rows, long long cap, long long S, int L, int D, int n_conv, int k) {
+    if (S <= 0 || L < 1 || n_conv < (ragged ? 1 : 0) || n_conv > ENC_MAX_CONV || !ln_dwconv_ok(D, k) || D > 1024) return false;
+    return ragged ? rows > 0 && cap >= rows && (!pooled || D == 128) : rows == S * L && cap == rows;
 }
 
-// dout: (M, L, D), or (M, D) when pooled.  dx (M, L, D) receives the gradient of x (may be NULL).  grads in params order.
-extern "C" int stage_grp_encoder_bwd(const float* dout, const float* x, const float* pool_mask, const float* const* P,
-                                     float* const* Gr, float* dx, const void* arena, size_t arena_bytes, const int* flags,
-                                     void* tmp, size_t tmp_bytes, long long M, int L, int D, int n_conv, int k, float p,
+// conv layer i, first launch: LN(pending + cur) (+dropout) -> depthwise conv.  At i == 0 the position table is what is added: the dense
+// kernel takes it as a residual of period L, the ragged one as its own argument next to no residual
+int enc_conv_fwd(const int* const* T, const float* pending, const float* cur, const float* pe, int i, const float* const* Q,
+                 const EncArena& a, long long S, int L, int D, int k, float p, unsigned long long seed, void* st) {
+    if (T)
+        return stage_ln_dwconv_rag_fwd(pending, cur, i == 0 ? pe : nullptr, a.s[i], Q[0], Q[1], Q[2], Q[3], a.h[i], a.mean[i], a.rstd[i], T[2],
+                                       S, L, D, k, EPS_LN, p, seed, st);
+    return stage_ln_dwconv_fwd(pending, i == 0 ? pe : cur, i == 0 ? L : 0, a.s[i], Q[0], Q[1], Q[2], Q[3], a.h[i], a.mean[i], a.rstd[i], S, L, D,
+                               k, EPS_LN, p, seed, st);
+}
+int enc_conv_bwd(const int* const* T, const float* dh, int i, const float* const* Q, float* const* GQ, float* Gn, const float* G,
+                 const EncArena& a, long long S, int L, int D, int k, float p, unsigned long long seed, void* ws, void* st) {
+    const size_t wsb = stage_ln_dwconv_bwd_ws_bytes(D, k);
+    if (T)
+        return stage_ln_dwconv_rag_bwd(dh, a.s[i], a.mean[i], a.rstd[i], Q[0], Q[1], Q[2], Gn, G, GQ[0], GQ[1], GQ[2], GQ[3], T[2], S, L, D, k, p,
+                                       seed, ws, wsb, st);
+    return stage_ln_dwconv_bwd(dh, a.s[i], a.mean[i], a.rstd[i], Q[0], Q[1], Q[2], Gn, G, GQ[0], GQ[1], GQ[2], GQ[3], S, L, D, k, p, seed, ws, wsb,
+                               st);
+}
+// final LayerNorm over pending + cur, with the masked max when pooled; -> flags[n_conv].  Fused with the max: ragged always, dense
+// where stage_ln_masked_max_supported says so and a conv layer exported the sum (n_conv == 0: x + pe, period L, goes through the
+// plain LayerNorm)
+int enc_final_fwd(const int* const* T, const float* pending, const float* cur, const float* pe, const float* pool_mask,
+                  const float* const* F, float* out, const EncArena& a, int* fused, long long rows, long long S, long long out_rows, int L,
+                  int D, int n_conv, void* st) {
+    const bool pooled = pool_mask != nullptr;
+    *fused = pooled && (T || (n_conv > 0 && stage_ln_masked_max_supported(L, D)));
+    if (*fused && T) {
+        TRY(stage_rag_fill_pooled(out, a.idx, out_rows, D, st));
+        return stage_ln_masked_max_rag_fwd(pending, cur, a.sf, F[0], F[1], pool_mask, out, a.idx, a.meanf, a.rstdf, T[2], S, L, D, EPS_LN, st);
+    }
+    if (*fused) return stage_ln_masked_max_fwd(pending, cur, a.sf, F[0], F[1], pool_mask, out, a.idx, a.meanf, a.rstdf, S, L, D, EPS_LN, st);
+    float* y = pooled ? a.yf : out;
+    TRY(stage_layernorm_fwd(pending, n_conv ? cur : pe, n_conv ? 0 : L, a.sf, F[0], F[1], y, a.meanf, a.rstdf, rows, D, EPS_LN, 0.f, 0ull, st));
+    return pooled ? stage_masked_max_fwd(y, pool_mask, nullptr, out, a.idx, S, L, D, st) : 0;
+}
+// its backward: G = gradient of the last exported sum
+int enc_final_bwd(const int* const* T, const float* dout, const float* pool_mask, const float* const* F, float* const* GF, float* G,
+                  const EncArena& a, const EncTmp& t, int fused, long long rows, long long S, int L, int D, void* st) {
+    const size_t wsb = stage_ln_bwd_ws_bytes(D);
+    if (pool_mask && T)
+        return stage_ln_masked_max_rag_bwd(dout, a.idx, pool_mask, a.sf, a.meanf, a.rstdf, F[0], G, GF[0], GF[1], T[3], rows, D, t.ws, wsb, st);
+    if (pool_mask && fused)
+        return stage_ln_masked_max_bwd(dout, a.idx, pool_mask, a.sf, a.meanf, a.rstdf, F[0], G, GF[0], GF[1], S, L, D, t.ws, wsb, st);
+    if (pool_mask) TRY(stage_masked_max_bwd(dout, a.idx, pool_mask, t.dyf, S, L, D, 0, st));
+    return stage_layernorm_bwd(pool_mask ? t.dyf : dout, a.sf, a.meanf, a.rstdf, F[0], G, nullptr, GF[0], GF[1], rows, D, 0.f, 0ull, t.ws, wsb, st);
+}
+}  // namespace
+
+extern "C" size_t stage_grp_encoder_arena_bytes(long long cap, long long out_rows, int D, int n_conv, int pooled, int ragged) {
+    if (n_conv > ENC_MAX_CONV) return 0;
+    return enc_layout(nullptr, cap, out_rows, D, n_conv, pooled, ragged).bytes;
+}
+extern "C" size_t stage_grp_encoder_bwd_tmp_bytes(long long cap, int D, int k, int pooled, int ragged) {
+    return enc_tmp(nullptr, cap, D, k, pooled, ragged).bytes;
+}
+
+extern "C" int stage_grp_encoder_fwd(const float* x, const float* pe, const float* pool_mask, const float* const* P, float* out,
+                                     const int* const* T, void* arena, size_t arena_bytes, int* flags, long long rows, long long cap,
+                                     long long S, long long out_rows, int L, int D, int n_conv, int k, float p,
                                      const unsigned long long* seeds, void* st) {
-    (void)x;
-    const int pooled = pool_mask != nullptr;
-    if (n_conv < 0 || n_conv > ENC_MAX_CONV) return STAGE_ERR_SHAPE;
-    EncArena a = enc_layout((void*)arena, M, L, D, n_conv, pooled);
-    EncTmp t = enc_tmp(tmp, M, L, D, k, pooled);
+    const int pooled = pool_mask != nullptr, ragged = T != nullptr;
+    if (!enc_ok(ragged, pooled, rows, cap, S, L, D, n_conv, k)) return STAGE_ERR_SHAPE;
+    if (!ragged) out_rows = S;
+    EncArena a = enc_layout(arena, cap, out_rows, D, n_conv, pooled, ragged);
+    if (arena_bytes < a.bytes) return STAGE_ERR_WORKSPACE;
+    const float* pending = x;
+    const float* cur = nullptr;
+    for (int i = 0; i < n_conv; i++) {
+        const float* const* Q = P + 6 * i;
+        const bool drop = (i % 2) == 0;
+        TRY(enc_conv_fwd(T, pending, cur, pe, i, Q, a, S, L, D, k, drop ? p : 0.f, drop ? seeds[i / 2] : 0ull, st));
+        cur = a.s[i];
+        TRY(lin_fwd(a.h[i], Q[4], Q[5], a.g[i], a.mask[i], &flags[i], rows, D, D, 1, st));
+        pending = a.g[i];
+    }
+    return enc_final_fwd(T, pending, cur, pe, pool_mask, P + 6 * n_conv, out, a, &flags[n_conv], rows, S, out_rows, L, D, n_conv, st);
+}
+
+// dout: shaped as the forward's out.  dx (rows, D) receives the gradient of x (may be NULL).  grads in params order.
+extern "C" int stage_grp_encoder_bwd(const float* dout, const float* pool_mask, const float* const* P, float* const* Gr, float* dx,
+                                     const int* const* T, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
+                                     size_t tmp_bytes, long long rows, long long cap, long long S, long long out_rows, int L, int D,
+                                     int n_conv, int k, float p, const unsigned long long* seeds, void* st) {
+    const int pooled = pool_mask != nullptr, ragged = T != nullptr;
+    if (!enc_ok(ragged, pooled, rows, cap, S, L, D, n_conv, k)) return STAGE_ERR_SHAPE;
+    EncArena a = enc_layout((void*)arena, cap, ragged ? out_rows : S, D, n_conv, pooled, ragged);
+    EncTmp t = enc_tmp(tmp, cap, D, k, pooled, ragged);
     if (arena_bytes < a.bytes || tmp_bytes < t.bytes) return STAGE_ERR_WORKSPACE;
-    const long long R = M * L;
-    const float* const* F = P + 6 * n_conv;
-    float* const* GF = Gr + 6 * n_conv;
     // G = gradient of the last exported sum (pending + cur): it feeds the last 1x1 conv's output AND the previous sum
     float* G = (n_conv == 0 && dx) ? dx : t.Ga;
-    if (pooled && flags[n_conv]) {
-        TRY(stage_ln_masked_max_bwd(dout, a.idx, pool_mask, a.sf, a.meanf, a.rstdf, F[0], G, GF[0], GF[1], M, L, D, t.ws, stage_ln_bwd_ws_bytes(D), st));
-    } else {
-        const float* dy = dout;
-        if (pooled) {
-            TRY(stage_masked_max_bwd(dout, a.idx, pool_mask, t.dyf, M, L, D, 0, st));
-            dy = t.dyf;
-        }
-        TRY(stage_layernorm_bwd(dy, a.sf, a.meanf, a.rstdf, F[0], G, nullptr, GF[0], GF[1], R, D, 0.f, 0ull, t.ws, stage_ln_bwd_ws_bytes(D), st));
-    }
+    TRY(enc_final_bwd(T, dout, pool_mask, P + 6 * n_conv, Gr + 6 * n_conv, G, a, t, flags[n_conv], rows, S, L, D, st));
     for (int i = n_conv - 1; i >= 0; i--) {
         const float* const* Q = P + 6 * i;
         float* const* GQ = Gr + 6 * i;
         const bool drop = (i % 2) == 0;
-        const unsigned long long seed = drop ? seeds[i / 2] : 0ull;
         // 1x1 conv + ReLU: G is the gradient of its output; its input was the depthwise conv's output h[i]
-        TRY(lin_bwd(G, a.h[i], a.g[i], a.mask[i], flags[i], 1, Q[4], t.wt, t.dh, GQ[4], GQ[5], R, D, D, t.ws, t.wsb, st));
+        TRY(lin_bwd(G, a.h[i], a.g[i], a.mask[i], flags[i], 1, Q[4], t.wt, t.dh, GQ[4], GQ[5], rows, D, D, t.ws, t.wsb, st));
         // LayerNorm -> depthwise conv: gradient of the sum s[i] = LN-path gradient + what reached the sum directly (G)
         float* Gn = (i == 0 && dx) ? dx : (G == t.Ga ? t.Gb : t.Ga);
-        TRY(stage_ln_dwconv_bwd(t.dh, a.s[i], a.mean[i], a.rstd[i], Q[0], Q[1], Q[2], Gn, G, GQ[0], GQ[1], GQ[2], GQ[3], M, L, D, k,
-                                drop ? p : 0.f, seed, t.ws, stage_ln_dwconv_bwd_ws_bytes(D, k), st));
+        TRY(enc_conv_bwd(T, t.dh, i, Q, GQ, Gn, G, a, S, L, D, k, drop ? p : 0.f, drop ? seeds[i / 2] : 0ull, t.ws, st));
         G = Gn;
     }
     return 0;
@@ -674,7 +702,8 @@ extern "C" int stage_grp_temporal_head_bwd(const float* d_first, const float* d_
 //                 (Uc rows in all: its valid words / regions + the halo of the input encoder's convolutions); NULL: dense (N, Li, Lr, D)
 // G3r  as G3; `mixed` is (U, D) compact, S_raw / S_norm stay dense.  The backward overwrites the arena's copy of the attention
 //      output with its gradient (in place: a row is read before it is written): ONE backward per forward.
-// G2r  as G2 pooled: x (U, D) compact, out (N*NA*Li, D) dense; n_conv >= 1; the word mask comes from qa_mask (N*NA, Lqa).
+// G2   with these tables (above): rows = U, cap = Ucap, L = Lqa; pooled over the statement rows, out (N*NA*Li, D), the word mask is
+//      qa_mask (N*NA, Lqa); unpooled over a ragged context stream (T[2] = one entry per live frame), out (U, D).
 // =====================================================================================================================
 namespace {
 struct QaRagArena { float *Cn, *A, *z, *mean, *rstd; unsigned* mask; void* fwd_ws; size_t bytes; };
@@ -772,111 +801,6 @@ extern "C" int stage_grp_qa_ctx_rag_bwd(const float* d_mixed, const float* dS_ex
                                     t.ws, stage_str_attn_bwd_fused_ws_bytes(N, NA, Li, Lqa, D), st));
     TRY(stage_l2norm_bwd(t.dCn, qa, d_qa, Crows, D, EPS_L2, p, seeds[0], 1, st));
     return stage_l2norm_bwd(t.dQn, ctx, d_ctx, Qrows, D, EPS_L2, p, seeds[1], 1, st);
-}
-
-namespace {
-EncArena enc_rag_layout(void* base, long long Ucap, long long Rd, int D, int n_conv) {
-    Bump b{(char*)base, 0};
-    EncArena a;
-    const size_t R = (size_t)Ucap;
-    for (int i = 0; i < n_conv; i++) {
-        a.h[i] = b.take<float>(R * D);
-        a.s[i] = b.take<float>(R * D);
-        a.mean[i] = b.take<float>(R);
-        a.rstd[i] = b.take<float>(R);
-        a.g[i] = b.take<float>(R * D);
-        a.mask[i] = b.take<unsigned>(lin_mask_words((long long)R, D));
-    }
-    a.sf = b.take<float>(R * D);
-    a.meanf = b.take<float>(R);
-    a.rstdf = b.take<float>(R);
-    a.yf = nullptr;
-    a.idx = b.take<int>((size_t)Rd * D);
-    a.bytes = b.off;
-    return a;
-}
-EncTmp enc_rag_tmp(void* base, long long Ucap, int D, int k) {
-    Bump b{(char*)base, 0};
-    EncTmp t;
-    const size_t R = (size_t)Ucap;
-    t.Ga = b.take<float>(R * D);
-    t.Gb = b.take<float>(R * D);
-    t.dh = b.take<float>(R * D);
-    t.dyf = nullptr;
-    t.wt = b.take<float>((size_t)D * D);
-    t.wsb = umax(umax(stage_ln_bwd_ws_bytes(D), stage_ln_dwconv_bwd_ws_bytes(D, k)), lin_bwd_ws(Ucap, D, D));
-    t.ws = b.take<char>(t.wsb);
-    t.bytes = b.off;
-    return t;
-}
-}  // namespace
-
-extern "C" size_t stage_grp_encoder_rag_arena_bytes(long long Ucap, long long Rd, int D, int n_conv) {
-    if (n_conv > ENC_MAX_CONV) return 0;
-    return enc_rag_layout(nullptr, Ucap, Rd, D, n_conv).bytes;
-}
-extern "C" size_t stage_grp_encoder_rag_bwd_tmp_bytes(long long Ucap, int D, int k) { return enc_rag_tmp(nullptr, Ucap, D, k).bytes; }
-
-// x (U, D) compact; pe (>= Lqa, D) position table; qa_mask (groups, Lqa); out (Rd, D) dense: the masked max over the words of every
-// (group, frame).  T as above (seq has S entries).  qa_mask == NULL: no pooling -- out is (U, D), the block's output on the same
-// ragged sequences (the input encoder over a ragged context stream: T[2] = one entry per live frame, Rd is ignored)
-extern "C" int stage_grp_encoder_rag_fwd(const float* x, const float* pe, const float* qa_mask, const float* const* P, float* out,
-                                         const int* const* T, void* arena, size_t arena_bytes, int* flags, long long U, long long Ucap,
-                                         long long S, long long Rd, int Lqa, int D, int n_conv, int k, float p,
-                                         const unsigned long long* seeds, void* st) {
-    const bool pooled = qa_mask != nullptr;
-    if (U <= 0 || S <= 0 || Ucap < U || n_conv < 1 || n_conv > ENC_MAX_CONV || !ln_dwconv_ok(D, k) || (pooled && D != 128) || Lqa < 1 || D > 1024)
-        return STAGE_ERR_SHAPE;
-    if (!pooled) Rd = 0;
-    EncArena a = enc_rag_layout(arena, Ucap, Rd, D, n_conv);
-    if (arena_bytes < a.bytes) return STAGE_ERR_WORKSPACE;
-    const float* pending = x;
-    const float* cur = nullptr;
-    for (int i = 0; i < n_conv; i++) {
-        const float* const* Q = P + 6 * i;
-        const bool drop = (i % 2) == 0;
-        const unsigned long long seed = drop ? seeds[i / 2] : 0ull;
-        TRY(stage_ln_dwconv_rag_fwd(pending, cur, i == 0 ? pe : nullptr, a.s[i], Q[0], Q[1], Q[2], Q[3], a.h[i], a.mean[i], a.rstd[i], T[2], S,
-                                    Lqa, D, k, EPS_LN, drop ? p : 0.f, seed, st));
-        cur = a.s[i];
-        TRY(lin_fwd(a.h[i], Q[4], Q[5], a.g[i], a.mask[i], &flags[i], U, D, D, 1, st));
-        pending = a.g[i];
-    }
-    const float* const* F = P + 6 * n_conv;
-    flags[n_conv] = pooled ? 1 : 0;
-    if (!pooled) return stage_layernorm_fwd(pending, cur, 0, a.sf, F[0], F[1], out, a.meanf, a.rstdf, U, D, EPS_LN, 0.f, 0ull, st);
-    TRY(stage_rag_fill_pooled(out, a.idx, Rd, D, st));
-    return stage_ln_masked_max_rag_fwd(pending, cur, a.sf, F[0], F[1], qa_mask, out, a.idx, a.meanf, a.rstdf, T[2], S, Lqa, D, EPS_LN, st);
-}
-
-// dout (Rd, D) dense; dx (U, D) compact (may be NULL); grads in params order
-extern "C" int stage_grp_encoder_rag_bwd(const float* dout, const float* qa_mask, const float* const* P, float* const* Gr, float* dx,
-                                         const int* const* T, const void* arena, size_t arena_bytes, const int* flags, void* tmp,
-                                         size_t tmp_bytes, long long U, long long Ucap, long long S, long long Rd, int Lqa, int D,
-                                         int n_conv, int k, float p, const unsigned long long* seeds, void* st) {
-    if (n_conv < 1 || n_conv > ENC_MAX_CONV) return STAGE_ERR_SHAPE;
-    const bool pooled = qa_mask != nullptr;
-    if (!pooled) Rd = 0;
-    EncArena a = enc_rag_layout((void*)arena, Ucap, Rd, D, n_conv);
-    EncTmp t = enc_rag_tmp(tmp, Ucap, D, k);
-    if (arena_bytes < a.bytes || tmp_bytes < t.bytes) return STAGE_ERR_WORKSPACE;
-    const float* const* F = P + 6 * n_conv;
-    float* const* GF = Gr + 6 * n_conv;
-    float* G = t.Ga;
-    if (pooled) TRY(stage_ln_masked_max_rag_bwd(dout, a.idx, qa_mask, a.sf, a.meanf, a.rstdf, F[0], G, GF[0], GF[1], T[3], U, D, t.ws, stage_ln_bwd_ws_bytes(D), st));
-    else TRY(stage_layernorm_bwd(dout, a.sf, a.meanf, a.rstdf, F[0], G, nullptr, GF[0], GF[1], U, D, 0.f, 0ull, t.ws, stage_ln_bwd_ws_bytes(D), st));
-    for (int i = n_conv - 1; i >= 0; i--) {
-        const float* const* Q = P + 6 * i;
-        float* const* GQ = Gr + 6 * i;
-        const bool drop = (i % 2) == 0;
-        const unsigned long long seed = drop ? seeds[i / 2] : 0ull;
-        TRY(lin_bwd(G, a.h[i], a.g[i], a.mask[i], flags[i], 1, Q[4], t.wt, t.dh, GQ[4], GQ[5], U, D, D, t.ws, t.wsb, st));
-        float* Gn = (i == 0 && dx) ? dx : (G == t.Ga ? t.Gb : t.Ga);
-        TRY(stage_ln_dwconv_rag_bwd(t.dh, a.s[i], a.mean[i], a.rstd[i], Q[0], Q[1], Q[2], Gn, G, GQ[0], GQ[1], GQ[2], GQ[3], T[2], S, Lqa, D, k,
-                                    drop ? p : 0.f, seed, t.ws, stage_ln_dwconv_bwd_ws_bytes(D, k), st));
-        G = Gn;
-    }
-    return 0;
 }
 
 // =====================================================================================================================

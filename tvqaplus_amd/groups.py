@@ -253,47 +253,60 @@ def input_mlp_rag(x, clay, l2: bool, p: float, seeds, params):
 # ---------------------------------------------------------------------------------------------------------------
 class _Encoder(torch.autograd.Function):
     @_on_device
-    def forward(ctx, x, pe, pool_mask, k: int, p: float, seeds, *params):
-        x = _chk(x, "x")                       # (M, L, D)
+    def forward(ctx, x, pe, pool_mask, lay, k: int, p: float, seeds, *params):
+        x = _chk(x, "x")                       # (S, L, D); with a layout: its (U, D) compact rows
         pe = _chk(pe, "pe")
+        pm = _chk(pool_mask, "pool_mask") if pool_mask is not None else None
         ctx.sinks = _sinks(params)
         params = _params(params)
-        M, L, D = x.shape
+        D = x.shape[-1]
         n_conv = (len(params) - 2) // 6
-        pooled = pool_mask is not None
-        pm = _chk(pool_mask, "pool_mask") if pooled else None
-        lib = _lib.load()
-        ab = _size("stage_grp_encoder_arena_bytes", M, L, D, n_conv, int(pooled))
+        if lay is None:
+            S, L, _ = x.shape
+            rows, cap, out_rows, T = S * L, S * L, S, None
+            out = torch.empty((S, D) if pm is not None else (S, L, D), dtype=torch.float32, device=x.device)
+        else:
+            assert x.shape[0] == lay.U
+            rows, cap, S, L, T = lay.U, lay.Ucap, lay.S, lay.Lqa, lay.T
+            out_rows = lay.out_rows if pm is not None else 0
+            out = torch.empty(out_rows, D, dtype=torch.float32, device=x.device) if pm is not None else _rows(rows, D, x.device)
+        form = (int(pm is not None), int(lay is not None))
+        dims = (rows, cap, S, out_rows, L, D, n_conv, int(k), float(p))
+        ab = _size("stage_grp_encoder_arena_bytes", cap, out_rows, D, n_conv, *form)
         arena = _buf(ab, x.device)
-        out = torch.empty((M, D) if pooled else (M, L, D), dtype=torch.float32, device=x.device)
         flags = _flags()
-        _rc(lib.stage_grp_encoder_fwd(x.data_ptr(), pe.data_ptr(), None if pm is None else pm.data_ptr(), _ptrs(params), out.data_ptr(),
-                                      arena.data_ptr(), ab, flags, M, L, D, n_conv, int(k), float(p), _u64(seeds), _stream()),
+        _rc(_lib.load().stage_grp_encoder_fwd(x.data_ptr(), pe.data_ptr(), None if pm is None else pm.data_ptr(), _ptrs(params),
+                                              out.data_ptr(), T, arena.data_ptr(), ab, flags, *dims, _u64(seeds), _stream()),
             "stage_grp_encoder_fwd")
-        ctx.save_for_backward(x, pm, arena, *params)
-        ctx.cfg = (M, L, D, n_conv, int(k), float(p), tuple(seeds), flags, ab, pooled)
+        ctx.save_for_backward(pm, arena, *params)
+        ctx.cfg = (dims, form, x.shape, tuple(seeds), flags, ab)
+        ctx.lay = lay
         return out
 
     @_on_device
     def backward(ctx, dout):
-        x, pm, arena, *params = ctx.saved_tensors
-        M, L, D, n_conv, k, p, seeds, flags, ab, pooled = ctx.cfg
+        pm, arena, *params = ctx.saved_tensors
+        dims, form, xshape, seeds, flags, ab = ctx.cfg
+        rows, cap, D, k = dims[0], dims[1], dims[5], dims[7]
+        lay = ctx.lay
         dout = _chk(dout, "dout")
-        lib = _lib.load()
         grads = _grad_views(params)
-        dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        tb = _size("stage_grp_encoder_bwd_tmp_bytes", M, L, D, k, int(pooled))
-        tmp = _buf(tb, x.device)
-        _rc(lib.stage_grp_encoder_bwd(dout.data_ptr(), x.data_ptr(), None if pm is None else pm.data_ptr(), _ptrs(params), _ptrs(grads),
-                                      None if dx is None else dx.data_ptr(), arena.data_ptr(), ab, flags, tmp.data_ptr(), tb, M, L, D,
-                                      n_conv, k, p, _u64(seeds), _stream()), "stage_grp_encoder_bwd")
-        return (dx, None, None, None, None, None) + _deliver(ctx.sinks, grads)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            # shaped like x; ragged: the first U rows of a buffer of Ucap rows (a few distinct allocation sizes per run)
+            dx = torch.empty(xshape if lay is None else (cap, D), dtype=torch.float32, device=dout.device)[:xshape[0]]
+        tb = _size("stage_grp_encoder_bwd_tmp_bytes", cap, D, k, *form)
+        tmp = _buf(tb, dout.device)
+        _rc(_lib.load().stage_grp_encoder_bwd(dout.data_ptr(), None if pm is None else pm.data_ptr(), _ptrs(params), _ptrs(grads),
+                                              None if dx is None else dx.data_ptr(), None if lay is None else lay.T, arena.data_ptr(), ab,
+                                              flags, tmp.data_ptr(), tb, *dims, _u64(seeds), _stream()), "stage_grp_encoder_bwd")
+        return (dx, None, None, None, None, None, None) + _deliver(ctx.sinks, grads)
 
 
 def encoder_block(x, pe, pool_mask, k: int, p: float, seeds, params):
     """x (M, L, D) -> (M, L, D), or (M, D) = masked max over L when ``pool_mask`` (M, L) is given.
     params: per conv (ln.w ln.b dw.w dw.b pw.w pw.b), then final_ln.w final_ln.b."""
-    return _Encoder.apply(x, pe, pool_mask, k, p, tuple(seeds), *params)
+    return _Encoder.apply(x, pe, pool_mask, None, k, p, tuple(seeds), *params)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -418,55 +431,11 @@ def qa_ctx_rag(qa, cx, qa_mask, cx_mask, lay, clay, scale: float, p: float, seed
     return _QaCtxRag.apply(qa, cx, qa_mask, cx_mask, lay, clay, scale, p, tuple(seeds), *params)
 
 
-class _EncoderRag(torch.autograd.Function):
-    @_on_device
-    def forward(ctx, x, pe, qa_mask, lay, k: int, p: float, seeds, *params):
-        x = _chk(x, "x")                       # (U, D) compact
-        pe = _chk(pe, "pe")
-        qa_mask = _chk(qa_mask, "qa_mask") if qa_mask is not None else None
-        ctx.sinks = _sinks(params)
-        params = _params(params)
-        U, D = x.shape
-        assert U == lay.U
-        n_conv = (len(params) - 2) // 6
-        Rd = lay.out_rows if qa_mask is not None else 0
-        lib = _lib.load()
-        ab = _size("stage_grp_encoder_rag_arena_bytes", lay.Ucap, Rd, D, n_conv)
-        arena = _buf(ab, x.device)
-        out = torch.empty(Rd, D, dtype=torch.float32, device=x.device) if qa_mask is not None else _rows(U, D, x.device)
-        flags = _flags()
-        _rc(lib.stage_grp_encoder_rag_fwd(x.data_ptr(), pe.data_ptr(), None if qa_mask is None else qa_mask.data_ptr(), _ptrs(params),
-                                          out.data_ptr(), lay.T,
-                                          arena.data_ptr(), ab, flags, lay.U, lay.Ucap, lay.S, Rd, lay.Lqa, D, n_conv, int(k), float(p),
-                                          _u64(seeds), _stream()), "stage_grp_encoder_rag_fwd")
-        ctx.save_for_backward(qa_mask, arena, *params)
-        ctx.cfg = (U, D, Rd, n_conv, int(k), float(p), tuple(seeds), flags, ab)
-        ctx.lay = lay
-        return out
-
-    @_on_device
-    def backward(ctx, dout):
-        qa_mask, arena, *params = ctx.saved_tensors
-        U, D, Rd, n_conv, k, p, seeds, flags, ab = ctx.cfg
-        lay = ctx.lay
-        dout = _chk(dout, "dout")
-        lib = _lib.load()
-        grads = _grad_views(params)
-        dx = torch.empty(lay.Ucap, D, dtype=torch.float32, device=dout.device)[:U] if ctx.needs_input_grad[0] else None
-        tb = _size("stage_grp_encoder_rag_bwd_tmp_bytes", lay.Ucap, D, k)
-        tmp = _buf(tb, dout.device)
-        _rc(lib.stage_grp_encoder_rag_bwd(dout.data_ptr(), None if qa_mask is None else qa_mask.data_ptr(), _ptrs(params), _ptrs(grads),
-                                          None if dx is None else dx.data_ptr(), lay.T, arena.data_ptr(), ab, flags, tmp.data_ptr(), tb,
-                                          lay.U, lay.Ucap, lay.S, Rd, lay.Lqa, D, n_conv, k, p, _u64(seeds), _stream()),
-            "stage_grp_encoder_rag_bwd")
-        return (dx, None, None, None, None, None, None) + _deliver(ctx.sinks, grads)
-
-
 def encoder_block_rag(x, pe, qa_mask, lay, k: int, p: float, seeds, params):
     """x (U, D) compact rows of ``lay`` -> (N*NA*Li, D): the classifier encoder block + the masked max over the words of every
     (example, candidate, frame) (model/stage.py:502-503); qa_mask (N*NA, Lqa).  qa_mask None: no pooling, (U, D) comes back -- an
     encoder block over the ragged sequences of a context stream (``lay`` a ``ragged.CtxLayout``)."""
-    return _EncoderRag.apply(x, pe, qa_mask, lay, k, p, tuple(seeds), *params)
+    return _Encoder.apply(x, pe, qa_mask, lay, k, p, tuple(seeds), *params)
 
 
 # ---------------------------------------------------------------------------------------------------------------

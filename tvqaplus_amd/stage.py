@@ -472,16 +472,23 @@ class STAGE(nn.Module):
         return ops.layernorm(x, self._g(ln.weight), self._g(ln.bias), p=self._p() if drop else 0.0, seed=self._seed() if drop else 0,
                              res=res, res_period=res_period)
 
+    def _encoder_group(self, x, blk: _EncoderBlockParams, L: int, pool_mask=None, lay=None):
+        """One conv-only encoder block as its K-group, with one dropout seed per even conv layer.  x (M, L, D): ``None`` when the C
+        side declines the shape (_try_group).  With ``lay``: x holds the compact rows of that ragged layout, and a refusal raises."""
+        k = blk.conv[0].depthwise_conv.weight.shape[-1]
+        params = [self._g(w) for w in _block_params(blk)]
+        pe, n_seeds = blk.position_encoding.rows(L), (blk.n_conv + 1) // 2
+        if lay is None:
+            return self._try_group(lambda seeds: groups.encoder_block(x, pe, pool_mask, k, self._p(), seeds, params), n_seeds)
+        return groups.encoder_block_rag(x, pe, pool_mask, lay, k, self._p(), self._seeds(n_seeds), params)
+
     def _encoder_block(self, x, mask, blk: _EncoderBlockParams, pool_mask=None):
         """model/encoder.py:29-52.  x (M, L, D).  Residual adds are deferred into the next LayerNorm's prologue.
         ``pool_mask`` (M, L): the caller only needs the masked max of the block's output over L (the classifier head,
         model/stage.py:503) -- the final LayerNorm and the max run as one pass and (M, D) is returned."""
         M, L, D = x.shape
         if self._grouped() and blk.num_heads == 0 and blk.n_conv >= 1 and x.dtype == torch.float32:
-            k = blk.conv[0].depthwise_conv.weight.shape[-1]
-            params = [self._g(w) for w in _block_params(blk)]
-            y = self._try_group(lambda seeds: groups.encoder_block(x, blk.position_encoding.rows(L), pool_mask, k, self._p(), seeds,
-                                                                   params), (blk.n_conv + 1) // 2)
+            y = self._encoder_group(x, blk, L, pool_mask)
             if y is not None:
                 return y
         pending, cur, period = x, blk.position_encoding.rows(L), L  # first LN sees x + pe[:L]
@@ -566,10 +573,7 @@ class STAGE(nn.Module):
                 mc = data_mask.index_select(0, clay.live_frames.long()).contiguous()
                 return self._stacked_encoder(y.view(clay.S, L, -1), mc, input_encoder).reshape(clay.U, -1)
             for blk in input_encoder.stacked_encoderBlocks:
-                bp = _block_params(blk)
-                k = blk.conv[0].depthwise_conv.weight.shape[-1]
-                y = groups.encoder_block_rag(y, blk.position_encoding.rows(L), None, clay, k, self._p(),
-                                             self._seeds((blk.n_conv + 1) // 2), [self._g(w) for w in bp])
+                y = self._encoder_group(y, blk, L, lay=clay)
             return y
         grouped = self._grouped() and not self.fuse_input_ln
         # half-precision features, fp32 model: tried as they are (converted in registers by the group's first kernel -- no fp32 copy to
@@ -726,11 +730,7 @@ class STAGE(nn.Module):
             mx_c = self._stacked_encoder(statement.view(lay.S, Lqa, D), ms, self.cls_encoder, pool_mask=ms)
             mx = torch.full((N * NA * Li, D), NEG, dtype=mx_c.dtype, device=mx_c.device).index_copy(0, seq_out, mx_c)
         elif lay is not None:
-            blk = self.cls_encoder.stacked_encoderBlocks[0]
-            params = _block_params(blk)
-            k = blk.conv[0].depthwise_conv.weight.shape[-1]
-            mx = groups.encoder_block_rag(statement, blk.position_encoding.rows(Lqa), qa_mask.reshape(N * NA, Lqa).contiguous(), lay, k,
-                                          self._p(), self._seeds((blk.n_conv + 1) // 2), [self._g(w) for w in params])
+            mx = self._encoder_group(statement, self.cls_encoder.stacked_encoderBlocks[0], Lqa, qa_mask.reshape(N * NA, Lqa).contiguous(), lay)
         else:
             x = statement.reshape(N * NA * Li, Lqa, D)
             mx = self._stacked_encoder(x, m, self.cls_encoder, pool_mask=m)            # encoder + :503 (max over the words)
